@@ -23,8 +23,14 @@ plane (barriers, the RCCL id, the max of the per-rank times).
 Inputs are synthetic (uwvk.synth) and resident in HBM before timing starts.
 Timing: barrier + device sync on both sides of the timed region, max over
 ranks; the dominant kernel's average launch time comes from HIP events on the
-handle's stream.  cpu_baseline: the fp64 C oracle (oracle/, "port") on a
-bounded sample of the same workload, on rank 0 at N = 1 only.
+handle's stream.
+
+A plain run sets up, warms up, times --steps epochs and prints the line.
+--full adds what the headline figure does not need: cpu_baseline, the fp64 C
+oracle (oracle/, "port") on a bounded sample of the same workload, on rank 0 at
+N = 1 only; and at N > 1 collective_check, the all-reduced statistics against
+the host sum.  --dump-outputs DIR writes the filter state after the last timed
+step (dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -146,7 +152,13 @@ def parse():
                          "cycle (0.25%% efforts epochs) inside a 2000-epoch window")
     ap.add_argument("--vel-groups", type=int, default=-1, help="C2: -1 auto, 0 lane per filter, 1 16-lane rows, 2 16-lane rows each run twice "
                          "in a 32-lane group (diagnostic: twice the waves, same work per wave)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baseline (cpu_baseline, N = 1) and the "
+                         "untimed check of the all-reduced statistics against the host sum (collective_check, N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (the state "
+                         "get_state returns, the status words, the ensemble statistics) as DIR/<name>.npy")
     ap.add_argument("--dense", action="store_true", help="literal kernels (all 2n+1 sigma points)")
     ap.add_argument("--so3-left", action="store_true",
                     help="UWVK_OPT_SO3_RIGHT = 0: the nav-frame SO3 boxplus exp(d) q instead of the default body-frame "
@@ -230,6 +242,39 @@ def timed_run(f, dlog, base, e_from, e_to, cut_abs, reduce_stats, truth, dof, ba
     f.synchronize()
     barrier()
     return time.perf_counter() - t0, f.timer_elapsed(), stats, len(pts)
+
+
+# --dump-outputs: the means of every instance while they fit DUMP_MEAN_BYTES and
+# the covariances of a fixed, seeded sample of DUMP_SAMPLE instances (n = 53:
+# 23 MB), so that a dump stays below 64 MB whatever the batch
+DUMP_SAMPLE = 1024
+DUMP_MEAN_BYTES = 32 << 20
+DUMP_SEED = 53
+
+
+def dump_sample(batch):
+    """The instances --dump-outputs samples: all of a small batch, else a
+    fixed seeded choice (sorted), the same from run to run."""
+    if batch <= DUMP_SAMPLE:
+        return np.arange(batch)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(batch, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(dirname, x, P, extra=None, rank=0, world=1):
+    """Write the state after the last timed step as DIR/<name>.npy (float64):
+    state_mean (every instance, or the sample's when they exceed
+    DUMP_MEAN_BYTES), state_cov of the sampled instances, sample_instances
+    (their indices within this rank's shard) and the arrays of `extra`.  A
+    rank of an N > 1 job writes <name>_rankR.npy.  Returns the names written."""
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_sample(len(x))
+    arrays = {"state_mean": x if x.nbytes <= DUMP_MEAN_BYTES else x[idx], "state_cov": P[idx],
+              "sample_instances": idx}
+    arrays.update(extra or {})
+    tag = "" if world == 1 else "_rank%d" % rank
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + tag + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    return sorted(name + tag for name in arrays)
 
 
 def pmc_entry(workload, steps=None):
@@ -659,10 +704,10 @@ def main():
         w = torch.tensor([wall, kernel_ms], dtype=torch.float64)
         dist.all_reduce(w, op=dist.ReduceOp.MAX)
         wall, kernel_ms = float(w[0]), float(w[1])
-    # untimed check of the collective: the RCCL sum equals the gloo sum of the
+    # untimed check of the collective (--full): the RCCL sum equals the gloo sum of the
     # per-rank statistics (same fixed-order kernel sums on every rank)
     coll_check = None
-    if dist is not None and world > 1:
+    if a.full and dist is not None and world > 1:
         local_st = f.ensemble_stats(truth.state(e0 + a.steps, a.dof))
         host_sum = ensemble.allreduce_stats(local_st, dist)
         # the two sums add the same per-rank values in different orders: they
@@ -675,6 +720,11 @@ def main():
     status = f.get_status()
     if status.any():
         print("warning: %d instances flagged (status bits)" % int((status != 0).sum()), file=sys.stderr)
+    dumped = None
+    if a.dump_outputs:
+        x, P = f.get_state()
+        dumped = dump_outputs(a.dump_outputs, x, P, {"status": status, "ensemble_stats": stats}, rank, world)
+        del x, P
 
     steps_total = B * world * a.steps
     value = steps_total / wall
@@ -792,7 +842,9 @@ def main():
         "ensemble": {"nees_mean_pos_ori_vel": float(stats[-2] / max(1.0, B * world - stats[-1])),
                      "nees_excluded_instances": int(stats[-1])},
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if dumped:
+        out["dumped_outputs"] = dumped
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(synth, cfg, uwv, log_mode, a.dof, a.cpu_threads or available_cores(),
                                            a.init, right=not a.so3_left)
     if rank == 0:
@@ -833,6 +885,10 @@ def bench_c1(a):
             counts = o.run_log(log, nthreads=1)
             dt = time.perf_counter() - t0
             x, P = o.get_state()
+            if a.dump_outputs:
+                os.makedirs(a.dump_outputs, exist_ok=True)
+                np.save(os.path.join(a.dump_outputs, "state_mean_dof%d.npy" % dof), np.asarray(x, np.float64))
+                np.save(os.path.join(a.dump_outputs, "state_cov_dof%d.npy" % dof), np.asarray(P, np.float64))
             res[dof] = {"value": epochs / dt, "seconds": dt, "epochs": epochs,
                         "dvl_updates": int(((log["flags"] & 2) != 0).sum()),
                         "accepted_updates": [int(v) for v in counts[0]],
@@ -911,7 +967,10 @@ def bench_vel(a, engine, synth, world, rank, local, dist, B):
                                                "note": "the same time priced at the reference's formulation "
                                                        "(two rotations for the restoring forces); not a roofline"}},
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.dump_outputs:
+        x, P = f.get_state()
+        out["dumped_outputs"] = dump_outputs(a.dump_outputs, x, P, rank=rank, world=world)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         threads = a.cpu_threads or available_cores()
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_ctypes as O

@@ -5,6 +5,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,6 +66,50 @@ def test_bench_line_fields_documented():
         assert key in src
     d = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
     assert "C3-dof53-b65536-e20" in d and "C3-dof53-b65536-left-e20" in d
+
+
+def test_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """--full is off by default and switches on what the headline does not need."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    assert np.array_equal(bench.dump_sample(10), np.arange(10))
+    s = bench.dump_sample(65536)
+    assert np.array_equal(s, bench.dump_sample(65536))  # the same from run to run
+    assert len(s) == bench.DUMP_SAMPLE == len(set(s.tolist())) and np.all(np.diff(s) > 0)
+    assert 0 <= s[0] and s[-1] < 65536
+    # the headline shapes stay below 64 MB: means (C3 all, C5 the sample's), sampled covariances, status, statistics
+    for batch in (65536, 131072):
+        mean = batch * 54 * 8
+        mean = mean if mean <= bench.DUMP_MEAN_BYTES else bench.DUMP_SAMPLE * 54 * 8
+        assert mean + bench.DUMP_SAMPLE * (53 * 53 + 1) * 8 + batch * 8 + 164 * 8 < 64 << 20
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path, monkeypatch):
+    rng = np.random.default_rng(1)
+    B = 3000
+    x, P = rng.normal(size=(B, 54)), rng.normal(size=(B, 5, 5))
+    status = np.zeros(B, np.uint32)
+    status[17] = 6
+    names = bench.dump_outputs(str(tmp_path / "d"), x, P, {"status": status})
+    assert names == ["sample_instances", "state_cov", "state_mean", "status"]
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    idx = got["sample_instances"].astype(np.int64)
+    assert np.array_equal(idx, bench.dump_sample(B))
+    assert np.array_equal(got["state_mean"], x) and np.array_equal(got["state_cov"], P[idx])
+    assert got["status"][17] == 6 and got["status"].sum() == 6
+    # means beyond the byte bound: the sample's rows; a rank of an N > 1 job tags its files
+    monkeypatch.setattr(bench, "DUMP_MEAN_BYTES", 1000)
+    names = bench.dump_outputs(str(tmp_path / "d"), x, P, rank=1, world=2)
+    assert names == ["sample_instances_rank1", "state_cov_rank1", "state_mean_rank1"]
+    assert np.array_equal(np.load(str(tmp_path / "d" / "state_mean_rank1.npy")), x[idx])
 
 
 # ---- multi-GPU launch logic (no GPU: spawned scripts stand in for the ranks) ----

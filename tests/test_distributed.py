@@ -277,7 +277,7 @@ def test_bench_self_launches_ranks(ranks):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "20", "--warmup",
-                        "2", "--batch-per-gpu", "16384", "--no-cpu-baseline"], capture_output=True, text=True,
+                        "2", "--batch-per-gpu", "16384", "--full", "--no-cpu-baseline"], capture_output=True, text=True,
                        timeout=500, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
