@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #define UWVK_DEV __device__ __forceinline__
 
 namespace uwvk {
@@ -53,6 +55,24 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 #define UWVK_DEVICE_GUARD(h) ::uwvk::DeviceGuard uwvk_device_guard_((h) ? (h)->device : -1)
+
+// in a C-ABI function: a failing HIP call ends it with UWVK_EDEVICE and is
+// recorded for uwvk_last_device_error
+#define HIPCHK(x)                                  \
+  do {                                             \
+    const hipError_t e_ = (x);                     \
+    if (e_ != hipSuccess) {                        \
+      ::uwvk::note_hip_error((int)e_, __func__);   \
+      return UWVK_EDEVICE;                         \
+    }                                              \
+  } while (0)
+
+// checkMeasurment [EXT]: no NaN / Inf in a host array
+inline bool finite_all(const double* a, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if (!std::isfinite(a[k])) return false;
+  return true;
+}
 
 constexpr double kEarthW = 7.292115e-5;  // pose_estimation::EARTHW [EXT] (PoseUKF.cpp:30)
 constexpr double kD2P95 = 5.991;         // PoseUKF.cpp:275-286

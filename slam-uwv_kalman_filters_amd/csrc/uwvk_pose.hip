@@ -1,16 +1,11 @@
-// uwvk_pose.hip — PoseUKF kernels (gfx950) and the uwvk_pose_* C ABI.
-//
-// Grid: one 64-thread workgroup (= one wavefront) per filter instance.
-// Every kernel loads (mu, Sigma) of its instance into LDS once, runs one or
-// more predict / update steps on it and writes it back.  The fused epoch
-// kernel (k_pose_epoch) is the hot path of uwvk_pose_run_log:
-//   RotationRate -> predictionStep(dt) -> Acceleration update
-//   [-> Velocity (DVL) -> Pressure -> ADCP cells -> BodyEfforts]
-// with Sigma resident in LDS across all steps of the epoch.
-#include <array>
-#include <map>
+// uwvk_pose.hip — the uwvk_pose_* C ABI: the handle, its buffers, the copies
+// and the launches.  No kernels here: they are instantiated in the
+// uwvk_pose_k_*.hip and uwvk_psp_*.hip translation units (launchers in
+// uwvk_pose_kernels.hpp / uwvk_psp.hpp), and what uwvk_pose_run_log launches is
+// decided by the pure host planner in uwvk_plan.hpp.
 #include "uwvk_pose_kernels.hpp"
 #include "uwvk_psp.hpp"
+#include "uwvk_plan.hpp"
 #include "uwvk_host.hpp"
 #include "uwvk_aug_dev.hpp"
 
@@ -58,7 +53,6 @@ struct uwvk_pose {
   // last-generation spreading of the PSP epoch launch (UWVK_OPT_TAIL_SLOTS)
   int64_t tail_slots = 0;  // resident blocks per XCD to plan for: 0 auto, < 0 off
   int tail_force = 0;      // UWVK_OPT_TAIL_CHUNKS: >= 2 forces that many chunks (tests)
-  std::map<std::array<int64_t, 3>, int> tail_chunks;  // (instances per XCD, slots, epochs) -> chunks
   uint32_t* d_tail_flag = nullptr;  // per tail instance (batch / 8 - 1 per XCD at most)
   double* d_tail_carry = nullptr;   // per tail instance: 64 x (ds, ids)
   int64_t tail_inst_cap = 0;
@@ -128,119 +122,35 @@ static void set_shared(uwvk_pose* h, const uwvk_pose_parameter& p, const uwvk_lo
   }
 }
 
-// PSP kernels read the batch-shared parameters and dt^2 Q (packed) from device memory
-// lane-resident Q (psp::LaneQ): no coupling of the rewritten rows (< 9) with
-// anything but their own diagonal / the orientation block, and a band of at
-// most 2 below the diagonal in rows >= 9 (the epoch kernel's QM = 1)
-static bool q_is_simple(const uwvk_pose* h) {
-  const int n = h->dof;
-  auto Qij = [&](int i, int j) { return h->Qh.empty() ? 0.0 : h->Qh[(size_t)i * n + j]; };
-  for (int i = 0; i < n; i++)
-    for (int j = 0; j < i; j++) {
-      if (Qij(i, j) == 0.0) continue;
-      const bool ori = i >= 3 && i < 6 && j >= 3 && j < 6;
-      if ((i < 9 || j < 9) ? !ori : (i - j > 2)) return false;
-    }
-  return true;
+// what run_log's kernel choice depends on (uwvk_plan.hpp: runs_pd, runs_pair),
+// with the Q shape of the current host Q
+static EpochFacts facts(const uwvk_pose* h) {
+  return {h->dof, h->batch, h->pd_opt, h->pair_opt, h->persist, h->lds_pad, use_dense(h), h->pdec,
+          q_is_simple(h->dof, h->Qh), q_params_diag(h->dof, h->Qh)};
 }
 
-// the process noise leaves the parameter block decoupled: no Q entry in a
-// parameter row / column (tangent 19..45) off the diagonal
-static bool q_params_diag(const uwvk_pose* h) {
-  if (h->dof != 53) return false;
-  if (h->Qh.empty()) return true;
-  for (int i = 0; i < 53; i++)
-    for (int j = 0; j < 53; j++)
-      if (i != j && ((i >= 19 && i <= 45) || (j >= 19 && j <= 45)) && h->Qh[(size_t)i * 53 + j] != 0.0) return false;
-  return true;
-}
-// the next PSP epoch launch runs the parameter-decoupled kernel (after
-// upload_shared: q_simple is the current Q's)
-static bool use_pd(const uwvk_pose* h) {
-  return h->pd_opt && h->pdec && h->dof == 53 && h->sh.q_simple && q_params_diag(h);
-}
-
-// the two-instances-per-wave kernel (UWVK_OPT_PAIR): the parameter-decoupled
-// state of a 53-DOF handle, or a 26-DOF handle's own state (r06), on the
-// persistent scheduler, an even batch, the lane-resident Q and no LDS pad
-static bool pair_eligible(uwvk_pose* h) {
-  if (!h->pair_opt || !h->persist || h->batch % 2 != 0 || h->lds_pad != 0 || use_dense(h)) return false;
-  if (h->dof == 26) return q_is_simple(h);
-  return h->pd_opt && h->pdec && h->dof == 53 && q_is_simple(h) && q_params_diag(h);  // (uwvk_pose_param_block)
-}
-
+// PSP kernels read the batch-shared parameters and dt^2 Q (packed) from device
+// memory: the tables of build_q_tables, uploaded once per dt
 static hipError_t upload_shared(uwvk_pose* h, double dt) {
   hipError_t e = hipSuccess;
   if (dt != h->qp_dt) {
-    const int n = h->dof;
-    // A_ii: the diagonal of the process model's Jacobian, the same expressions as
-    // psp::proc_diag (1 + dt (-1/tau) per Markov block, 1 otherwise)
-    std::vector<double> ad(n, 1.0);
-    auto block = [&](int d0, int len, double nt) {
-      for (int d = d0; d < d0 + len; d++) ad[d] = 1.0 + dt * nt;
+    const QTables t = build_q_tables(h->dof, h->Qh, h->sh.ntau, dt);
+    static_assert(sizeof(t.qlo) == sizeof(h->sh.qlo) && sizeof(t.qoff) == sizeof(h->sh.qoff), "PoseShared's band");
+    static_assert(Lay<53>::d_bg == 12 && Lay<53>::d_ba == 15 && Lay<53>::d_inertia == 19 && Lay<53>::d_wv == 46 &&
+                      Lay<53>::d_rho == 52 && Lay<26>::d_wv == 19 && Lay<26>::d_rho == 25,
+                  "the Markov blocks of build_q_tables");
+    std::memcpy(h->sh.qlo, t.qlo, sizeof(t.qlo));
+    std::memcpy(h->sh.qoff, t.qoff, sizeof(t.qoff));
+    h->sh.q_band = t.q_band;
+    h->sh.q_bw = t.q_bw;
+    h->sh.q_simple = t.q_simple;
+    auto upload = [&](double* d, const std::vector<double>& v) {
+      return hipMemcpyAsync(d, v.data(), v.size() * 8, hipMemcpyHostToDevice, h->stream);
     };
-    const double* nt = h->sh.ntau;
-    if (n == 53) {
-      using L = Lay<53>;
-      block(L::d_bg, 3, nt[0]); block(L::d_ba, 3, nt[1]); block(L::d_inertia, 9, nt[2]);
-      block(L::d_lin, 9, nt[3]); block(L::d_quad, 9, nt[4]); block(L::d_wv, 4, nt[5]);
-      block(L::d_badcp, 2, nt[6]); block(L::d_rho, 1, nt[7]);
-    } else {
-      using L = Lay<26>;
-      block(L::d_bg, 3, nt[0]); block(L::d_ba, 3, nt[1]); block(L::d_wv, 4, nt[5]);
-      block(L::d_badcp, 2, nt[6]); block(L::d_rho, 1, nt[7]);
-    }
-    auto rewritten = [](int d) { return d < 9; };  // pos, ori, vel rows: rewritten by the kernel
-    auto Qij = [&](int i, int j) { return h->Qh.empty() ? 0.0 : h->Qh[(size_t)i * n + j]; };
-    std::vector<double> qp((size_t)n * (n + 1));
-    const double dt2 = dt * dt;
-    for (int i = 0, k = 0; i < n; i++)
-      for (int j = 0; j <= i; j++, k++) {
-        qp[2 * k] = (rewritten(i) || rewritten(j)) ? 0.0 : ad[i] * ad[j];
-        qp[2 * k + 1] = dt2 * Qij(i, j);
-      }
-    // band of rows >= 9: first nonzero column >= 9 .. diagonal
-    std::vector<double> band(128, 0.0);
-    int off = 0;
-    bool fits = true;
-    for (int i = 0; i < n; i++) {
-      int lo = i + 1;
-      if (i >= 9)
-        for (int j = 9; j <= i; j++)
-          if (Qij(i, j) != 0.0) { lo = j; break; }
-      h->sh.qlo[i] = lo;
-      h->sh.qoff[i] = off;
-      for (int j = lo; j <= i; j++, off++) {
-        if (off < 128) band[off] = dt2 * Qij(i, j);
-        else fits = false;
-      }
-    }
-    h->sh.q_band = fits ? 1 : 0;
-    int bw = 0;
-    for (int i = 9; i < n; i++) bw = std::max(bw, i - h->sh.qlo[i]);
-    h->sh.q_bw = bw;
-    h->sh.q_simple = q_is_simple(h) ? 1 : 0;
-    e = hipMemcpyAsync(h->d_Qp, qp.data(), qp.size() * 8, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_qband, band.data(), 128 * 8, hipMemcpyHostToDevice, h->stream);
-    // the PD kernel's table: the 26-DOF subset's entries in its packed order,
-    // then parameter t's (19 + t, 19 + t) entry at 351 + t (psp::lane_q PD)
-    std::vector<double> qpd((351 + 32) * 2, 0.0);
-    if (n == 53) {
-      auto m = [](int d) { return d < 19 ? d : d + 27; };
-      for (int i = 0, k = 0; i < 26; i++)
-        for (int j = 0; j <= i; j++, k++) {
-          const int I = m(i), J = m(j), k53 = I * (I + 1) / 2 + J;
-          qpd[2 * k] = qp[2 * k53];
-          qpd[2 * k + 1] = qp[2 * k53 + 1];
-        }
-      for (int t = 0; t < 27; t++) {
-        const int d = 19 + t, k53 = d * (d + 1) / 2 + d;
-        qpd[2 * (351 + t)] = qp[2 * k53];
-        qpd[2 * (351 + t) + 1] = qp[2 * k53 + 1];
-      }
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_Qp_pd, qpd.data(), qpd.size() * 8, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // qp, band are locals
+    e = upload(h->d_Qp, t.qp);
+    if (e == hipSuccess) e = upload(h->d_qband, t.band);
+    if (e == hipSuccess) e = upload(h->d_Qp_pd, t.qpd);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the tables are locals
     if (e != hipSuccess) return e;
     h->qp_dt = dt;
   }
@@ -251,22 +161,6 @@ static hipError_t upload_shared(uwvk_pose* h, double dt) {
   h->sh_dev_ok = e == hipSuccess;
   if (h->sh_dev_ok) h->sh_dev = h->sh;
   return e;
-}
-
-#define HIPCHK(x)                                  \
-  do {                                             \
-    const hipError_t e_ = (x);                     \
-    if (e_ != hipSuccess) {                        \
-      ::uwvk::note_hip_error((int)e_, __func__);   \
-      return UWVK_EDEVICE;                         \
-    }                                              \
-  } while (0)
-
-
-static bool finite_all(const double* a, size_t n) {
-  for (size_t k = 0; k < n; k++)
-    if (!std::isfinite(a[k])) return false;
-  return true;
 }
 
 extern "C" {
@@ -296,8 +190,8 @@ uwvk_status uwvk_pose_create(int64_t batch, int dof, int device, uwvk_pose** out
             hipMalloc(&h->d_meas, B * 74 * 8) == hipSuccess && hipMalloc(&h->d_mask, B) == hipSuccess &&
             hipMalloc(&h->d_accepted, B) == hipSuccess && hipMalloc(&h->d_scratch, (B * 3 + 256 + ((B + 63) / 64) * kStatsMaxOut) * 8) == hipSuccess &&
             hipMalloc(&h->d_shared, sizeof(PoseShared)) == hipSuccess &&
-            hipMalloc(&h->d_Qp, n * (n + 1) * 8) == hipSuccess && hipMalloc(&h->d_qband, 128 * 8) == hipSuccess &&
-            hipMalloc(&h->d_Qp_pd, (351 + 32) * 2 * 8) == hipSuccess &&
+            hipMalloc(&h->d_Qp, n * (n + 1) * 8) == hipSuccess && hipMalloc(&h->d_qband, kQBand * 8) == hipSuccess &&
+            hipMalloc(&h->d_Qp_pd, kQpdEntries * 2 * 8) == hipSuccess &&
             hipMalloc(&h->d_ticket, 4) == hipSuccess &&
             hipHostMalloc((void**)&h->h_fault, 4, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
             hipHostGetDevicePointer((void**)&h->d_fault, h->h_fault, 0) == hipSuccess &&
@@ -342,11 +236,7 @@ int uwvk_pose_dof(const uwvk_pose* h) { return h ? h->dof : 0; }
 void* uwvk_pose_stream(const uwvk_pose* h) { return h ? (void*)h->stream : nullptr; }
 // a tail-chunk hand-off that timed out in a launch that has completed (the
 // kernel wrote the handle's host-mapped fault word); reported once
-static bool take_fault(uwvk_pose* h) {
-  if (!__atomic_load_n(h->h_fault, __ATOMIC_ACQUIRE)) return false;
-  __atomic_store_n(h->h_fault, 0u, __ATOMIC_RELEASE);
-  return true;
-}
+static bool take_fault(uwvk_pose* h) { return __atomic_exchange_n(h->h_fault, 0u, __ATOMIC_ACQ_REL) != 0; }
 
 uwvk_status uwvk_pose_synchronize(uwvk_pose* h) {
   UWVK_DEVICE_GUARD(h);
@@ -378,20 +268,7 @@ static uwvk_status upload_state(uwvk_pose* h, const std::vector<double>& x, cons
     for (int i = 0, k = 0; i < h->dof; i++)
       for (int j = 0; j <= i; j++, k++) Pp[b * tn + k] = P[(b * h->dof + i) * h->dof + j];
   HIPCHK(hipMemcpyAsync(h->d_sigma, Pp.data(), Pp.size() * 8, hipMemcpyHostToDevice, h->stream));
-  // the parameter block decoupled (PD kernel): every lower-triangle entry in a
-  // parameter row or column (tangent 19..45) off the diagonal is zero
-  h->pdec = false;
-  if (h->dof == 53) {
-    bool dec = true;
-    for (int64_t b = 0; b < h->batch && dec; b++)
-      for (int i = 19, k0 = 19 * 20 / 2; i < 53 && dec; k0 += ++i)
-        for (int j = 0; j < i; j++)
-          if ((i <= 45 || (j >= 19 && j <= 45)) && Pp[b * tn + k0 + j] != 0.0) {
-            dec = false;
-            break;
-          }
-    h->pdec = dec;
-  }
+  h->pdec = param_block_decoupled(h->dof, h->batch, Pp.data());
   HIPCHK(hipMemcpyAsync(h->d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->d_model, model.data(), model.size() * 8, hipMemcpyHostToDevice, h->stream));
   double uw[108];
@@ -711,102 +588,6 @@ static hipError_t tail_buffers(uwvk_pose* h, int64_t need, int64_t cap) {
   return hipSuccess;
 }
 
-// chunk count of a launch: the planner's (cached per shape), or the forced one
-static int tail_plan(uwvk_pose* h, int64_t n, int64_t s, int64_t count) {
-  const std::array<int64_t, 3> key{n, s, count};
-  auto it = h->tail_chunks.find(key);
-  if (it == h->tail_chunks.end()) {
-    if (h->tail_chunks.size() >= 64) h->tail_chunks.clear();
-    it = h->tail_chunks.emplace(key, plan_tail(n, s, count)).first;
-  }
-  int c = it->second;
-  if (h->tail_force >= 2)  // forced (tests): every chunk count, where the shape allows it
-    c = (s > 0 && h->tail_force <= 8 && h->tail_force * s <= n && h->tail_force <= count) ? h->tail_force : 1;
-  return c;
-}
-
-// Persistent launch (UWVK_OPT_PERSIST): grid = resident blocks (or fewer
-// units); the last r = chunks x slots instances run as epoch chunks, claimed
-// in chunk order (uwvk_psp_k.hip, k_psp_epoch_p).  UWVK_OPT_TAIL_SLOTS < 0
-// turns the chunks off, > 0 plans for that many slots per XCD.
-// pair: the two-instances-per-wave kernel, whose units are pairs of instances
-static hipError_t prepare_persist(uwvk_pose* h, EpochArgs& ea, int64_t& grid, int pd, int pair = 0) {
-  const int64_t B = pair ? h->batch / 2 : h->batch;
-  const int64_t slots = pair ? psp_pair_slots(h->device) : psp_epoch_slots(h->dof, h->device, true, pd);
-  const int64_t s = h->tail_slots > 0 ? 8 * h->tail_slots : slots;
-  if (slots <= 0) return hipErrorInvalidValue;
-  ea.chunks = 1;
-  ea.tail0 = B;
-  ea.r_x = 0;
-  int c = h->tail_slots < 0 || h->lds_pad > 0 || s <= 0 ? 1 : tail_plan(h, B, s, ea.count);
-  // the pair kernel's default: no spreading (r06v, interleaved: off +2.4% at 20
-  // epochs, a tie at 200; forced 3 / 4 chunks -6% / -18% at 20); an explicit
-  // UWVK_OPT_TAIL_SLOTS > 0 or UWVK_OPT_TAIL_CHUNKS still spreads (tests)
-  if (pair && h->tail_slots == 0 && h->tail_force < 2) c = 1;
-  if (c > 1) {
-    const int64_t r = c * s;
-    hipError_t e = tail_buffers(h, r, 8 * s);
-    if (e != hipSuccess) return e;
-    ea.tail_flag = h->d_tail_flag;
-    ea.tail_carry = h->d_tail_carry;
-    ea.tail0 = B - r;
-    ea.r_x = r;
-    ea.chunks = c;
-    ea.tag = h->tail_tag;
-    // a chunk waits at most for its predecessor's unit and the unit its block
-    // held before it: ~2 of the launch's epochs per wave, see prepare_tail
-    ea.wait_bound = (uint32_t)std::min<uint64_t>(0xffffffffull, (1ull << 20) + 128ull * (uint64_t)ea.count);
-    if (h->wait_bound >= 0) ea.wait_bound = (uint32_t)h->wait_bound;
-  }
-  const int64_t units = ea.tail0 + (int64_t)ea.chunks * ea.r_x;
-  grid = std::min<int64_t>(units, slots);
-  ea.units = (uint32_t)units;
-  ea.ticket = h->d_ticket;
-  ea.ticket_base = h->ticket_next;
-  // the first grid units are the blocks' own; the counter then numbers units
-  // grid .. units - 1 and one failing ticket per block: units - grid + grid.
-  // ticket_next advances only once the launch is queued (commit_persist): a
-  // launch that fails leaves the device counter where it was
-  return hipSuccess;
-}
-
-// the tail layout of one PSP epoch launch (uwvk_psp_k.hip, plan_tail), cached
-// per (instances per XCD, slots, epochs); fills ea's tail fields and the grid
-static hipError_t prepare_tail(uwvk_pose* h, EpochArgs& ea, int64_t& grid, int pd) {
-  ea.chunks = 1;
-  ea.ticket = nullptr;
-  grid = 0;
-  if (h->persist) return prepare_persist(h, ea, grid, pd);
-  // an LDS pad lowers the resident blocks below what the tail plan assumes:
-  // no spreading then (UWVK_OPT_LDS_PAD is a diagnostic of the unspread launch)
-  if (h->tail_slots < 0 || h->lds_pad > 0 || h->batch % 8 != 0) return hipSuccess;
-  // placement not the round-robin the XCD-ordered tail plan needs (a
-  // partitioned device, another runtime): the ticket-ordered persistent
-  // launch spreads the tail without any placement assumption
-  if (!xcd_round_robin(h->device)) return prepare_persist(h, ea, grid, pd);
-  const int64_t n = h->batch / 8;
-  const int64_t s = h->tail_slots > 0 ? h->tail_slots : psp_epoch_slots_per_xcd(h->dof, h->device, pd);
-  const int c = tail_plan(h, n, s, ea.count);
-  if (c <= 1) return hipSuccess;
-  const int64_t r = c * s;
-  hipError_t e = tail_buffers(h, 8 * r, 8 * std::max<int64_t>(r, 8 * s));
-  if (e != hipSuccess) return e;
-  ea.tail_flag = h->d_tail_flag;
-  ea.tail_carry = h->d_tail_carry;
-  ea.n_x = n;
-  ea.tail0 = n - r;
-  ea.r_x = r;
-  ea.chunks = c;
-  ea.tag = h->tail_tag;
-  // a chunk waits at most for its predecessors' (c - 1) / c of the launch's
-  // epochs; one sleep is ~1.7 us and an epoch ~20 us per wave at full
-  // occupancy: 64 sleeps per epoch is a wide margin, plus ~2 s of slack
-  ea.wait_bound = (uint32_t)std::min<uint64_t>(0xffffffffull, (1ull << 20) + 64ull * (uint64_t)ea.count);
-  if (h->wait_bound >= 0) ea.wait_bound = (uint32_t)h->wait_bound;
-  grid = 8 * (n + (c - 1) * r);
-  return hipSuccess;
-}
-
 uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
                               uint32_t* accept_counts) {
   UWVK_DEVICE_GUARD(h);
@@ -839,11 +620,7 @@ uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t fi
     }
     return UWVK_OK;
   }
-  // PSP: one launch per run of epochs up to and including the next BodyEfforts
-  // epoch (its predict and other updates); that epoch's efforts update alone
-  // then runs in its own one-wave PSP kernel (k_psp_efforts: the full model or
-  // its velocity-only form; its own register / LDS budget).  Efforts is the
-  // last update of an epoch (the fused literal order), so the split is exact.
+  // PSP: the launches of plan_epochs (uwvk_plan.hpp), in order
   std::vector<uint32_t> fl;
   const uint32_t* hf = log->host_flags ? log->host_flags + first : nullptr;
   if (!hf && count > 0) {
@@ -857,31 +634,54 @@ uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t fi
   HIPCHK(upload_shared(h, log->dt));
   const PoseShared sh = h->sh;  // after upload_shared (it refreshes the Q shape)
   ea.fault = h->d_fault;
-  // one epoch-kernel launch over [s0, s1): the pair kernel or the one-instance
-  // PSP kernel (parameter-decoupled while eligible)
-  auto launch_seg = [&](int64_t s0, int64_t s1, bool use_pair) -> uwvk_status {  // (pair or one-instance)
-    ea.first = s0;
-    ea.count = s1 - s0;
-    ea.efforts_only = 0;
-    int64_t grid = 0;
-    uint32_t ev_any = 0;  // the event kinds of this launch's epochs (kernel choice)
-    for (int64_t k = s0; k < s1; k++) ev_any |= hf[k - first];
-    const int pd = use_pd(h) ? 1 : 0;
-    PoseBufs bl = b;
-    if (pd) bl.Qp = h->d_Qp_pd;
-    if (h->dof == 53 && !pd) use_pair = false;  // (the pair kernel runs a 53-DOF state decoupled only)
-    hipError_t le;
-    if (use_pair) {
-      ea.chunks = 1;
-      ea.ticket = nullptr;
-      HIPCHK(prepare_persist(h, ea, grid, pd, 1));
-      le = launch_psp_epoch_pair(h->stream, bl, sh, ea, grid, ev_any, pd);
-    } else {
-      HIPCHK(prepare_tail(h, ea, grid, pd));
-      le = launch_psp_epoch(h->dof, h->stream, bl, sh, ea, grid, ev_any, h->lds_pad, pd);
+  ea.efforts_only = 0;
+  const EpochPlan plan = plan_epochs(hf, first, count, facts(h));
+  for (const Launch& l : plan.launches) {
+    ea.first = l.first;
+    ea.count = l.count;
+    if (l.kind == EFFORTS) {
+      // constrainVelocity (PEffVO) or the full measurementEfforts (psp_update_eff)
+      if (!l.vo) h->pdec = false;  // the full model couples the parameters (PD off from here)
+      HIPCHK(launch_psp_efforts(h->dof, l.vo, h->stream, b, sh, ea));
+      continue;
     }
+    const bool pair = l.kind == EPOCH_PAIR;
+    // the pair kernel runs a 53-DOF state decoupled only (runs_pair implies runs_pd there)
+    if (pair && h->dof == 53 && !l.pd) return UWVK_EINVAL;
+    // the persistent, ticket-ordered launch: the pair kernel's only form, the
+    // default, and the static launch's stand-in where block placement is not
+    // the round-robin its XCD-ordered tail needs (a partitioned device, another
+    // runtime): tickets spread the tail without any placement assumption
+    const bool spread = static_may_spread(h->batch, h->tail_slots, h->lds_pad);
+    Geometry g;
+    ea.ticket = nullptr;
+    if (pair || h->persist || (spread && !xcd_round_robin(h->device))) {
+      const int64_t slots = pair ? psp_pair_slots(h->device) : psp_epoch_slots(h->dof, h->device, true, l.pd);
+      HIPCHK(slots > 0 ? hipSuccess : hipErrorInvalidValue);
+      g = persist_geometry(pair ? h->batch / 2 : h->batch, slots, h->tail_slots, h->tail_force, h->lds_pad, l.count,
+                           pair, h->wait_bound);
+      // ticket_next advances only once the launch is queued: a launch that
+      // fails leaves the device counter where it was
+      ea.ticket = h->d_ticket;
+      ea.ticket_base = h->ticket_next;
+    } else {
+      const int64_t slots = spread && h->tail_slots <= 0 ? psp_epoch_slots_per_xcd(h->dof, h->device, l.pd) : 0;
+      g = static_geometry(h->batch, slots, h->tail_slots, h->tail_force, h->lds_pad, l.count, h->wait_bound);
+    }
+    if (g.tail_need > 0) {
+      HIPCHK(tail_buffers(h, g.tail_need, g.tail_cap));
+      ea.tail_flag = h->d_tail_flag;
+      ea.tail_carry = h->d_tail_carry;
+      ea.tag = h->tail_tag;
+    }
+    ea.chunks = g.chunks; ea.n_x = g.n_x; ea.tail0 = g.tail0; ea.r_x = g.r_x;
+    ea.units = g.units; ea.wait_bound = g.wait_bound;
+    PoseBufs bl = b;
+    if (l.pd) bl.Qp = h->d_Qp_pd;
+    const hipError_t le = pair ? launch_psp_epoch_pair(h->stream, bl, sh, ea, g.grid, l.ev_any, l.pd)
+                               : launch_psp_epoch(h->dof, h->stream, bl, sh, ea, g.grid, l.ev_any, h->lds_pad, l.pd);
     if (le != hipSuccess) {
-      ::uwvk::note_hip_error((int)le, use_pair ? "launch_psp_epoch_pair" : "launch_psp_epoch");
+      ::uwvk::note_hip_error((int)le, pair ? "launch_psp_epoch_pair" : "launch_psp_epoch");
       // a persistent launch that did not run took no tickets: restart the
       // counter from zero (stream-ordered, before any later launch)
       if (ea.ticket) {
@@ -891,57 +691,6 @@ uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t fi
       return UWVK_EDEVICE;
     }
     if (ea.ticket) h->ticket_next += ea.units;  // the tickets the launch takes
-    return UWVK_OK;
-  };
-  int64_t e = first;
-  while (e < first + count) {
-    int64_t r = e;
-    while (r < first + count && !(hf[r - first] & UWVK_EV_EFFORTS)) r++;
-    const int64_t last = r < first + count ? r + 1 : r;
-    // the two-instances-per-wave form of the parameter-decoupled kernel
-    // (UWVK_OPT_PAIR; persistent, even batch) runs the epochs without a
-    // pressure update (its 39 sigma points do not fit a half-wave): a launch
-    // with pressure epochs is split around them when the runs between them are
-    // long (kPairMinRun epochs: each extra launch costs a Sigma round trip and
-    // a ramp), the pressure epochs and short runs on the one-instance kernel
-    const bool pair_ok = pair_eligible(h);
-    if (!pair_ok) {
-      const uwvk_status st = launch_seg(e, last, false);
-      if (st != UWVK_OK) return st;
-    } else {
-      constexpr int64_t kPairMinRun = 48;
-      int64_t s0 = e;  // start of the pending one-instance segment
-      int64_t k = e;
-      while (k < last) {
-        if (hf[k - first] & UWVK_EV_PRESSURE) { k++; continue; }
-        int64_t q = k;  // a run of epochs without pressure: [k, q)
-        while (q < last && !(hf[q - first] & UWVK_EV_PRESSURE)) q++;
-        if (q - k >= kPairMinRun || (k == e && q == last)) {
-          if (k > s0) {
-            const uwvk_status st = launch_seg(s0, k, false);
-            if (st != UWVK_OK) return st;
-          }
-          const uwvk_status st = launch_seg(k, q, true);
-          if (st != UWVK_OK) return st;
-          s0 = q;
-        }
-        k = q;
-      }
-      if (last > s0) {
-        const uwvk_status st = launch_seg(s0, last, false);
-        if (st != UWVK_OK) return st;
-      }
-    }
-    if (r < first + count) {
-      ea.first = r;
-      ea.count = 1;
-      ea.efforts_only = 0;
-      // constrainVelocity (PEffVO) or the full measurementEfforts (psp_update_eff)
-      const int vo = (hf[r - first] & UWVK_EV_EFFORTS_VELOCITY_ONLY) ? 1 : 0;
-      if (!vo) h->pdec = false;  // the full model couples the parameters (PD off from here)
-      HIPCHK(launch_psp_efforts(h->dof, vo, h->stream, b, sh, ea));
-    }
-    e = last;
   }
   return UWVK_OK;
 }
@@ -1028,17 +777,13 @@ int64_t uwvk_pose_resident_slots(int dof, int device) {
   return psp_epoch_slots_per_xcd(dof, device);
 }
 
-int uwvk_pose_param_block(uwvk_pose* h) {
-  if (!h) return 0;
-  // q_simple is refreshed by upload_shared; evaluate it on the current Q
-  return (h->pd_opt && h->pdec && h->dof == 53 && q_is_simple(h) && q_params_diag(h)) ? 1 : 0;
-}
+int uwvk_pose_param_block(uwvk_pose* h) { return (h && runs_pd(facts(h))) ? 1 : 0; }
 
-int uwvk_pose_pair_active(uwvk_pose* h) { return (h && pair_eligible(h)) ? 1 : 0; }
+int uwvk_pose_pair_active(uwvk_pose* h) { return (h && runs_pair(facts(h))) ? 1 : 0; }
 
 int uwvk_xcd_round_robin(int device) { return xcd_round_robin(device); }
 
-int uwvk_pose_epoch_qshape(const uwvk_pose* h) { return h ? (q_is_simple(h) ? 1 : 2) : 0; }
+int uwvk_pose_epoch_qshape(const uwvk_pose* h) { return h ? (q_is_simple(h->dof, h->Qh) ? 1 : 2) : 0; }
 
 int uwvk_pose_tail_chunks(int64_t instances_per_xcd, int64_t slots_per_xcd, int64_t epochs) {
   return plan_tail(instances_per_xcd, slots_per_xcd, epochs);

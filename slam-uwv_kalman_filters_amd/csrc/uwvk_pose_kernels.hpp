@@ -46,7 +46,7 @@ struct EpochArgs {
   // literal epoch kernel only: run just the BodyEfforts update of each epoch
   // (the PSP launch before it has done the epoch's predict and other updates)
   int efforts_only;
-  // PSP epoch kernel, last-generation spreading (uwvk_psp_k.hip, plan_tail):
+  // PSP epoch kernel, last-generation spreading (uwvk_plan.hpp, plan_tail):
   // chunks <= 1 = one block per instance over [first, first + count).
   // Otherwise (static k_psp_epoch) block b runs on XCD x = b & 7 at position i = b >> 3: whole
   // instance x n_x + i for i < tail0, else chunk k = (i - tail0) / r_x of tail

@@ -55,9 +55,7 @@ int64_t psp_epoch_slots_per_xcd(int dof, int device, int pd = 0);
 // epoch kernel on the device (occupancy x CUs), 0 if unknown; pd: the
 // parameter-decoupled kernel's
 int64_t psp_epoch_slots(int dof, int device, bool persist, int pd = 0);
-// chunks per tail instance for one XCD's n instances over s resident blocks in
-// a count-epoch launch (1: no tail spreading)
-int plan_tail(int64_t n, int64_t s, int64_t count);
+// (the chunks per tail instance of a launch: plan_tail, uwvk_plan.hpp)
 // the two-instances-per-wave parameter-decoupled kernel (uwvk_psp_pair.hip):
 // persistent only (ea.ticket), pair units (EpochArgs units / tail0 / r_x count
 // pairs of instances 2u, 2u + 1), the PD table in b.Qp, sh.q_simple

@@ -8,7 +8,7 @@
 // The host splits a launch after each BodyEfforts epoch (this kernel runs that
 // epoch's predict and other updates) and runs the efforts update alone on the
 // literal k_pose_efforts_epoch, whose HBM layout is shared.  With tail
-// spreading (EpochArgs::chunks > 1, plan_tail below) the last instances of
+// spreading (EpochArgs::chunks > 1, plan_tail in uwvk_plan.hpp) the last instances of
 // each XCD run as a few epoch chunks, one block each, handed on in order.
 #include <algorithm>
 #include <atomic>
@@ -1019,38 +1019,6 @@ int64_t psp_epoch_slots(int dof, int device, bool persist, int pd) {
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     return 0;
   return (int64_t)per_cu * cus;
-}
-
-// Last-generation spreading.  Blocks of one XCD are dispatched in order to
-// its s resident slots; wave speeds differ (the first generation's waves end
-// anywhere between 0.8 and 1.25 of the mean), so after a few generations the
-// slots free up at scattered times and a launch of whole-instance blocks of
-// duration D ends with a ramp: the slots idle for D / 2 on average while the
-// last blocks finish.  Spreading ends the launch on short blocks instead: the
-// last m = C s instances of each XCD run as C epoch chunks, grouped by chunk
-// (all chunk-0 blocks after the whole instances, then all chunk-1 blocks,
-// ...), so each group keeps the XCD busy for about D and a chunk's
-// predecessor, m blocks earlier, has long finished; the ramp shrinks to
-// D / (2 C), for (C - 1) m extra block prologues and epilogues (Sigma~ and
-// its time scale reloaded and stored, the IMU prefetch restarted: about 0.75
-// epoch each, r02 timeline).  C minimises
-// count / (2 C) + 0.3 C (C - 1) epochs; none below a 10 % gain or when the
-// XCD has under (C + 1) s instances.
-constexpr double kTailChunkOverhead = 0.75;  // epochs per extra chunk (r02 timeline)
-int plan_tail(int64_t n, int64_t s, int64_t count) {
-  if (s <= 0 || count < 4) return 1;
-  const double base = 0.5 * (double)count;
-  double best = 0.9 * base;
-  int chunks = 1;
-  for (int c = 2; c <= 8 && 2 * c <= count; c++) {
-    if (n < (c + 1) * s) break;
-    const double cost = (double)count / (2.0 * c) + kTailChunkOverhead * c * (c - 1);
-    if (cost < best) {
-      best = cost;
-      chunks = c;
-    }
-  }
-  return chunks;
 }
 
 #endif  // PSP_SIDE == 0

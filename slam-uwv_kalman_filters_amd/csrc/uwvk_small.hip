@@ -227,22 +227,7 @@ __global__ __launch_bounds__(IAE<SR>::BLOCK) void k_ipose_visual(SmallBufs b, Vi
 
 int64_t grid_of(int64_t batch, int ipb) { return (batch + ipb - 1) / ipb; }
 
-bool finite_all(const double* a, size_t n) {
-  for (size_t k = 0; k < n; k++)
-    if (!std::isfinite(a[k])) return false;
-  return true;
-}
-
 }  // namespace
-
-#define HIPCHK(x)                                  \
-  do {                                             \
-    const hipError_t e_ = (x);                     \
-    if (e_ != hipSuccess) {                        \
-      ::uwvk::note_hip_error((int)e_, __func__);   \
-      return UWVK_EDEVICE;                         \
-    }                                              \
-  } while (0)
 
 // ===========================================================================
 // host handles

@@ -839,22 +839,7 @@ static VelBufs vbufs(const uwvk_vel* h) {
   return b;
 }
 
-#define HIPCHK(x)                                  \
-  do {                                             \
-    const hipError_t e_ = (x);                     \
-    if (e_ != hipSuccess) {                        \
-      ::uwvk::note_hip_error((int)e_, __func__);   \
-      return UWVK_EDEVICE;                         \
-    }                                              \
-  } while (0)
-
 static unsigned vgrid(int64_t B) { return (unsigned)((B + 63) / 64); }
-
-static bool vfinite(const double* a, size_t n) {
-  for (size_t k = 0; k < n; k++)
-    if (!std::isfinite(a[k])) return false;
-  return true;
-}
 
 extern "C" {
 
@@ -919,7 +904,7 @@ uwvk_status uwvk_vel_set_option(uwvk_vel* h, int option, int value) {
 uwvk_status uwvk_vel_set_process_noise(uwvk_vel* h, const double Q[16]) {
   UWVK_DEVICE_GUARD(h);
   if (!h || !Q) return UWVK_EINVAL;
-  if (!vfinite(Q, 16)) return UWVK_ENAN;
+  if (!finite_all(Q, 16)) return UWVK_ENAN;
   std::memcpy(h->P.Q0, Q, sizeof(h->P.Q0));
   // after all queued work (a running kernel may read the previous copy)
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -993,7 +978,7 @@ uwvk_status uwvk_vel_setup_motion_model(uwvk_vel* h, const uwvk_uwv_params* u) {
 uwvk_status uwvk_vel_set_gyro(uwvk_vel* h, const double* w, const double* cov) {
   UWVK_DEVICE_GUARD(h);
   if (!h || !w) return UWVK_EINVAL;
-  if (!vfinite(w, (size_t)h->batch * 3) || (cov && !vfinite(cov, (size_t)h->batch * 9))) return UWVK_ENAN;
+  if (!finite_all(w, (size_t)h->batch * 3) || (cov && !finite_all(cov, (size_t)h->batch * 9))) return UWVK_ENAN;
   HIPCHK(hipMemcpyAsync(h->d_gyro, w, (size_t)h->batch * 3 * 8, hipMemcpyHostToDevice, h->stream));
   if (h->has_model) {
     hipLaunchKernelGGL(k_vel_gyro_to_model, dim3(vgrid(h->batch)), dim3(64), 0, h->stream, vbufs(h));
@@ -1006,7 +991,7 @@ uwvk_status uwvk_vel_set_gyro(uwvk_vel* h, const double* w, const double* cov) {
 uwvk_status uwvk_vel_set_efforts(uwvk_vel* h, const double* tau, const double* cov) {
   UWVK_DEVICE_GUARD(h);
   if (!h || !tau) return UWVK_EINVAL;
-  if (!vfinite(tau, (size_t)h->batch * 6) || (cov && !vfinite(cov, (size_t)h->batch * 36))) return UWVK_ENAN;
+  if (!finite_all(tau, (size_t)h->batch * 6) || (cov && !finite_all(cov, (size_t)h->batch * 36))) return UWVK_ENAN;
   HIPCHK(hipMemcpyAsync(h->d_eff, tau, (size_t)h->batch * 6 * 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return UWVK_OK;
@@ -1028,9 +1013,9 @@ static uwvk_status vel_update(uwvk_vel* h, int m, const double* mu, const double
   const int64_t B = h->batch;
   for (int64_t i = 0; i < B; i++) {
     if (mask && !mask[i]) continue;
-    if (!vfinite(mu + i * m, m) || (cov && !vfinite(cov + i * m * m, (size_t)m * m))) return UWVK_ENAN;
+    if (!finite_all(mu + i * m, m) || (cov && !finite_all(cov + i * m * m, (size_t)m * m))) return UWVK_ENAN;
   }
-  if (!cov && !vfinite(shared_cov, (size_t)m * m)) return UWVK_ENAN;
+  if (!cov && !finite_all(shared_cov, (size_t)m * m)) return UWVK_ENAN;
   double* dz = h->d_meas;
   double* dc = h->d_meas + B * 3;
   HIPCHK(hipMemcpyAsync(dz, mu, (size_t)B * m * 8, hipMemcpyHostToDevice, h->stream));

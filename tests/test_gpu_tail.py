@@ -1,5 +1,5 @@
 """Last-generation spreading of the PSP run_log launch (UWVK_OPT_TAIL_SLOTS,
-csrc/uwvk_psp_k.hip: plan_tail / tail_unit): the tail instances of each XCD
+csrc/uwvk_plan.hpp: plan_tail; csrc/uwvk_psp_k.hip: tail_unit): the tail instances of each XCD
 run as epoch chunks handed from block to block.  Sigma~ and its time scale are
 handed on unfolded, so the result must be bitwise the one-block-per-instance
 run: state, covariance, accept counts, status words and rotation rate.

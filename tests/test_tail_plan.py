@@ -1,5 +1,5 @@
 """Host logic of the last-generation spreading planner (UWVK_OPT_TAIL_SLOTS,
-csrc/uwvk_psp_k.hip plan_tail), through the host-only C-ABI query; no device
+csrc/uwvk_plan.hpp plan_tail), through the host-only C-ABI query; no device
 work.  A Python twin of the planner's cost model (count / (2 C) + 0.75 C (C - 1)
 epochs of ramp + extra block overhead, against count / 2 unspread) and of the
 kernel's block layout (tail_unit)."""
