@@ -45,7 +45,7 @@ extern "C" {
  *      (body-frame SO3 [+], MTK's SO3::boxplus; was 0, nav frame): a caller
  *      that wants the old convention sets the option to 0;
  *      new entry points uwvk_last_device_error, uwvk_synth_normal_at,
- *      uwvk_ipose_set_option;
+ *      uwvk_ipose_set_option, uwvk_pose_track_records, uwvk_pose_run_log_track;
  *      a tail-chunk hand-off that timed out is an error of the API, not only
  *      the instances' UWVK_ST_SCHEDULE bit: the next uwvk_pose_synchronize
  *      or uwvk_pose_run_log on the handle after the launch has completed
@@ -386,6 +386,40 @@ typedef struct uwvk_pose_log {
  * accept_counts (device, nullable): [batch][4] uint32 accepted DVL/pressure/ADCP/efforts. */
 uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
                               uint32_t* accept_counts);
+
+/* The filter's trajectory during a run: after every `every`-th epoch of the log
+ * a record of all instances is written to the caller's DEVICE buffers, on the
+ * handle's stream like the epochs themselves (no host synchronisation, no host
+ * copy).  A record epoch ends a launch, as a BodyEfforts epoch does; a small
+ * kernel then reads the state that launch stored. */
+typedef struct uwvk_pose_track {
+  int64_t every;        /* > 0.  A record is taken after each absolute epoch e of the log
+                           with (e + 1) % every == 0, after all of that epoch's updates
+                           (BodyEfforts included). */
+  int64_t capacity;     /* records each non-NULL buffer below can hold */
+  double* mean;         /* DEVICE [records][batch][store]   (nullable) */
+  double* variance;     /* DEVICE [records][batch][dof]     diagonal of Sigma (nullable) */
+  double* stats;        /* DEVICE [records][3*store+2]      layout of uwvk_pose_ensemble_stats (nullable) */
+  const double* truth;  /* HOST   [records][store], read before the call returns; NULL = that
+                           function's NULL truth.  Used only when stats != NULL. */
+} uwvk_pose_track;
+
+/* host only: the records of epochs [first, first+count),
+ * floor((first+count)/every) - floor(first/every); 0 for every <= 0 or a negative range */
+int64_t uwvk_pose_track_records(int64_t first, int64_t count, int64_t every);
+
+/* uwvk_pose_run_log with a track.  Record r of the call is the r-th record epoch
+ * inside [first, first+count); epochs are numbered from the log's start, so the
+ * records of calls over adjacent ranges concatenate to those of one call.
+ * The result is bitwise that of uwvk_pose_run_log on each segment between
+ * record epochs with uwvk_pose_get_state / uwvk_pose_ensemble_stats at each cut:
+ * every record, the final state, accept_counts and the kernel choice of later
+ * calls.  track == NULL is uwvk_pose_run_log.
+ * UWVK_EINVAL, with nothing queued and the state untouched: every <= 0; mean,
+ * variance and stats all NULL; capacity < uwvk_pose_track_records(first, count,
+ * every).  Otherwise the errors of uwvk_pose_run_log. */
+uwvk_status uwvk_pose_run_log_track(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
+                                    uint32_t* accept_counts, const uwvk_pose_track* track);
 
 /* Ensemble statistics over the batch (for Monte-Carlo runs):
  * out[0..store)        = sum_i x_i (orientation quaternion summed componentwise)

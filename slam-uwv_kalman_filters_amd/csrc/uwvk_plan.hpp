@@ -218,6 +218,32 @@ inline EpochPlan plan_epochs(const uint32_t* host_flags, int64_t first, int64_t 
   return p;
 }
 
+// The track of uwvk_pose_run_log_track: a record is taken after each absolute
+// epoch e with (e + 1) % every == 0.  Records in [first, first + count), every > 0:
+inline int64_t track_records(int64_t first, int64_t count, int64_t every) {
+  return (first + count) / every - first / every;
+}
+// [first, first + count) cut after every record epoch: the segments tile the
+// range in order, each ends at a record epoch (record) or, the last one, at the
+// range's end without one.  Each segment is planned by plan_epochs on its own,
+// so a tracked run is the untracked runs of its segments, launch for launch.
+struct TrackSegment {
+  int64_t first, count;
+  bool record;
+};
+inline std::vector<TrackSegment> track_segments(int64_t first, int64_t count, int64_t every) {
+  std::vector<TrackSegment> s;
+  const int64_t end = first + count;
+  for (int64_t e = first; e < end;) {
+    const int64_t next = (e / every + 1) * every;  // one past the next record epoch
+    const bool record = next <= end;
+    const int64_t stop = record ? next : end;
+    s.push_back({e, stop - e, record});
+    e = stop;
+  }
+  return s;
+}
+
 // Last-generation spreading.  Blocks of one XCD are dispatched in order to
 // its s resident slots; wave speeds differ (the first generation's waves end
 // anywhere between 0.8 and 1.25 of the mean), so after a few generations the

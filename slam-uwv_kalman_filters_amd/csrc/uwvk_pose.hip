@@ -6,6 +6,7 @@
 #include "uwvk_pose_kernels.hpp"
 #include "uwvk_psp.hpp"
 #include "uwvk_plan.hpp"
+#include "uwvk_track.hpp"
 #include "uwvk_host.hpp"
 #include "uwvk_aug_dev.hpp"
 
@@ -588,53 +589,33 @@ static hipError_t tail_buffers(uwvk_pose* h, int64_t need, int64_t cap) {
   return hipSuccess;
 }
 
-uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
-                              uint32_t* accept_counts) {
-  UWVK_DEVICE_GUARD(h);
-  if (!h || !log || first < 0 || count < 0 || first + count > log->epochs || log->adcp_cells > 8) return UWVK_EINVAL;
-  if (!h->has_state) return UWVK_ENOTINIT;
-  // ABI 3: a hand-off timeout of an earlier, completed launch is reported here
-  // (or by uwvk_pose_synchronize), before any new work is queued
-  if (take_fault(h)) return UWVK_ESCHEDULE;
-  EpochArgs ea{};
-  ea.flags = log->flags; ea.gyro = log->gyro; ea.acc = log->acc;
-  std::memcpy(ea.acc_cov, log->acc_cov, sizeof(ea.acc_cov));
-  ea.dvl_index = log->dvl_index; ea.dvl = log->dvl;
-  std::memcpy(ea.dvl_cov, log->dvl_cov, sizeof(ea.dvl_cov));
-  ea.p_index = log->pressure_index; ea.pressure = log->pressure; ea.p_cov = log->pressure_cov;
-  std::memcpy(ea.p_sens, log->pressure_sensor_in_imu, sizeof(ea.p_sens));
-  ea.a_index = log->adcp_index; ea.adcp = log->adcp; ea.cells = log->adcp_cells;
-  std::memcpy(ea.cw, log->adcp_cell_weighting, sizeof(ea.cw));
-  std::memcpy(ea.adcp_cov, log->adcp_cov, sizeof(ea.adcp_cov));
-  ea.e_index = log->efforts_index; ea.efforts = log->efforts;
-  std::memcpy(ea.e_cov, log->efforts_cov, sizeof(ea.e_cov));
-  ea.dt = log->dt;
-  ea.accept_counts = accept_counts;
-  PoseBufs b = bufs(h);
+// the ensemble statistics' truth, by value in the kernel arguments: no upload
+// in front of the kernel.  truth: host store-vector, or null (zeros, identity)
+static StatTruth stat_truth(const uwvk_pose* h, const double* truth) {
+  StatTruth t{};
+  if (truth) std::memcpy(t.v, truth, h->store * 8);
+  else t.v[3] = 1.0;
+  t.right = h->sh.so3_right;
+  return t;
+}
+// the ensemble partials' area, after the rotation-rate area: d_scratch + 256 + 3 batch
+static double* stats_partials(const uwvk_pose* h) { return h->d_scratch + 256 + 3 * h->batch; }
+
+// The launches of epochs [first, first + count), queued on the handle's stream.
+// ea: the log's arguments (a copy per call: the launch fields start cleared);
+// hf: the host flags of these epochs (PSP path); sh: the handle's PoseShared
+// after upload_shared.
+static uwvk_status run_epochs(uwvk_pose* h, const PoseBufs& b, const PoseShared& sh, EpochArgs ea, const uint32_t* hf,
+                              int64_t first, int64_t count) {
   if (use_dense(h)) {  // literal kernels: one fused launch per epoch
-    h->pdec = false;
     for (int64_t e = first; e < first + count; e++) {
       ea.first = e;
       ea.count = 1;
-      HIPCHK(launch_pose_epoch(h->dof, h->stream, b, h->sh, ea));
+      HIPCHK(launch_pose_epoch(h->dof, h->stream, b, sh, ea));
     }
     return UWVK_OK;
   }
   // PSP: the launches of plan_epochs (uwvk_plan.hpp), in order
-  std::vector<uint32_t> fl;
-  const uint32_t* hf = log->host_flags ? log->host_flags + first : nullptr;
-  if (!hf && count > 0) {
-    fl.resize((size_t)count);
-    HIPCHK(hipMemcpyAsync(fl.data(), log->flags + first, (size_t)count * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    hf = fl.data();
-  }
-  std::memcpy(h->sh.log_acc_cov, log->acc_cov, sizeof(h->sh.log_acc_cov));
-  std::memcpy(h->sh.log_dvl_cov, log->dvl_cov, sizeof(h->sh.log_dvl_cov));
-  HIPCHK(upload_shared(h, log->dt));
-  const PoseShared sh = h->sh;  // after upload_shared (it refreshes the Q shape)
-  ea.fault = h->d_fault;
-  ea.efforts_only = 0;
   const EpochPlan plan = plan_epochs(hf, first, count, facts(h));
   for (const Launch& l : plan.launches) {
     ea.first = l.first;
@@ -695,6 +676,89 @@ uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t fi
   return UWVK_OK;
 }
 
+int64_t uwvk_pose_track_records(int64_t first, int64_t count, int64_t every) {
+  return first < 0 || count < 0 || every <= 0 ? 0 : track_records(first, count, every);
+}
+
+// uwvk_pose_run_log (track == null: the whole range is one segment) and
+// uwvk_pose_run_log_track (the range cut after every record epoch,
+// track_segments; after a segment that ends in one, the snapshot of the state
+// its last launch stored, and the statistics, into record r's slots)
+static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
+                           uint32_t* accept_counts, const uwvk_pose_track* track) {
+  if (!h || !log || first < 0 || count < 0 || first + count > log->epochs || log->adcp_cells > 8) return UWVK_EINVAL;
+  if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->stats) ||
+                track->capacity < track_records(first, count, track->every)))
+    return UWVK_EINVAL;
+  if (!h->has_state) return UWVK_ENOTINIT;
+  // ABI 3: a hand-off timeout of an earlier, completed launch is reported here
+  // (or by uwvk_pose_synchronize), before any new work is queued
+  if (take_fault(h)) return UWVK_ESCHEDULE;
+  EpochArgs ea{};
+  ea.flags = log->flags; ea.gyro = log->gyro; ea.acc = log->acc;
+  std::memcpy(ea.acc_cov, log->acc_cov, sizeof(ea.acc_cov));
+  ea.dvl_index = log->dvl_index; ea.dvl = log->dvl;
+  std::memcpy(ea.dvl_cov, log->dvl_cov, sizeof(ea.dvl_cov));
+  ea.p_index = log->pressure_index; ea.pressure = log->pressure; ea.p_cov = log->pressure_cov;
+  std::memcpy(ea.p_sens, log->pressure_sensor_in_imu, sizeof(ea.p_sens));
+  ea.a_index = log->adcp_index; ea.adcp = log->adcp; ea.cells = log->adcp_cells;
+  std::memcpy(ea.cw, log->adcp_cell_weighting, sizeof(ea.cw));
+  std::memcpy(ea.adcp_cov, log->adcp_cov, sizeof(ea.adcp_cov));
+  ea.e_index = log->efforts_index; ea.efforts = log->efforts;
+  std::memcpy(ea.e_cov, log->efforts_cov, sizeof(ea.e_cov));
+  ea.dt = log->dt;
+  ea.accept_counts = accept_counts;
+  PoseBufs b = bufs(h);
+  std::vector<uint32_t> fl;
+  const uint32_t* hf = nullptr;  // the flags of epochs first .. first + count - 1 (PSP)
+  if (use_dense(h)) {
+    h->pdec = false;
+  } else {
+    hf = log->host_flags ? log->host_flags + first : nullptr;
+    if (!hf && count > 0) {
+      fl.resize((size_t)count);
+      HIPCHK(hipMemcpyAsync(fl.data(), log->flags + first, (size_t)count * 4, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+      hf = fl.data();
+    }
+    std::memcpy(h->sh.log_acc_cov, log->acc_cov, sizeof(h->sh.log_acc_cov));
+    std::memcpy(h->sh.log_dvl_cov, log->dvl_cov, sizeof(h->sh.log_dvl_cov));
+    HIPCHK(upload_shared(h, log->dt));
+    ea.fault = h->d_fault;
+    ea.efforts_only = 0;
+  }
+  const PoseShared sh = h->sh;  // after upload_shared (it refreshes the Q shape)
+  if (!track) return run_epochs(h, b, sh, ea, hf, first, count);
+  const int s = h->store, nout = 3 * s + 2;
+  int64_t r = 0;  // the next record of this call
+  for (const TrackSegment& seg : track_segments(first, count, track->every)) {
+    const uwvk_status st = run_epochs(h, b, sh, ea, hf ? hf + (seg.first - first) : nullptr, seg.first, seg.count);
+    if (st != UWVK_OK) return st;
+    if (!seg.record) continue;
+    if (track->mean || track->variance)
+      HIPCHK(launch_pose_track(h->dof, h->stream, h->d_mu, h->d_sigma, h->batch,
+                               track->mean ? track->mean + r * h->batch * s : nullptr,
+                               track->variance ? track->variance + r * h->batch * h->dof : nullptr));
+    if (track->stats)
+      HIPCHK(launch_pose_stats(h->dof, h->stream, b, stat_truth(h, track->truth ? track->truth + r * s : nullptr),
+                               track->stats + r * nout, stats_partials(h)));
+    r++;
+  }
+  return UWVK_OK;
+}
+
+uwvk_status uwvk_pose_run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
+                              uint32_t* accept_counts) {
+  UWVK_DEVICE_GUARD(h);
+  return run_log(h, log, first, count, accept_counts, nullptr);
+}
+
+uwvk_status uwvk_pose_run_log_track(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
+                                    uint32_t* accept_counts, const uwvk_pose_track* track) {
+  UWVK_DEVICE_GUARD(h);
+  return run_log(h, log, first, count, accept_counts, track);
+}
+
 uwvk_status uwvk_pose_ensemble_stats(uwvk_pose* h, const double* truth, double* out) {
   UWVK_DEVICE_GUARD(h);
   return uwvk_pose_ensemble_allreduce(h, truth, out, nullptr);
@@ -706,14 +770,8 @@ uwvk_status uwvk_pose_ensemble_allreduce(uwvk_pose* h, const double* truth, doub
   const int s = h->store;
   const int nout = 3 * s + 2;
   double* d_out = h->d_scratch;
-  StatTruth t{};  // by value in the kernel arguments: no upload in front of the kernel
-  if (truth) std::memcpy(t.v, truth, s * 8);
-  else t.v[3] = 1.0;
-  t.right = h->sh.so3_right;
-  // ensemble partials after the rotation-rate area: d_scratch + 256 + 3 batch
-  double* d_part = h->d_scratch + 256 + 3 * h->batch;
   PoseBufs b = bufs(h);
-  HIPCHK(launch_pose_stats(h->dof, h->stream, b, t, d_out, d_part));
+  HIPCHK(launch_pose_stats(h->dof, h->stream, b, stat_truth(h, truth), d_out, stats_partials(h)));
   if (comm) {  // RCCL sum across the ranks' shards, stream-ordered after the stats kernel
     const uwvk_status st = uwvk_comm_allreduce_sum_device(comm, d_out, nout, (void*)h->stream);
     if (st != UWVK_OK) return st;

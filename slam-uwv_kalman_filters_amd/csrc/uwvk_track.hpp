@@ -1,0 +1,14 @@
+// uwvk_track.hpp — the snapshot kernel of uwvk_pose_run_log_track (uwvk_track.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace uwvk {
+
+// One record of all instances, from the state the last launch stored to HBM:
+// mean [batch][store] = mu, variance [batch][dof] = the diagonal of the packed
+// lower triangle sigma.  Either output may be null (not both).
+hipError_t launch_pose_track(int dof, hipStream_t st, const double* mu, const double* sigma, int64_t batch,
+                             double* mean, double* variance);
+
+}  // namespace uwvk

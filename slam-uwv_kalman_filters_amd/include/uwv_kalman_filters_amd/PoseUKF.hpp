@@ -574,6 +574,13 @@ class PoseUKF {
   void runLog(const uwvk_pose_log& log, int64_t first, int64_t count, uint32_t* accept_counts = nullptr) {
     check(uwvk_pose_run_log(h_, &log, first, count, accept_counts), "runLog");
   }
+  // runLog with the filter's trajectory (uwvk_pose_run_log_track): after every
+  // track.every-th epoch of the log a record of all instances goes to the
+  // track's device buffers, on the handle's stream.
+  void runLogTrack(const uwvk_pose_log& log, int64_t first, int64_t count, const uwvk_pose_track& track,
+                   uint32_t* accept_counts = nullptr) {
+    check(uwvk_pose_run_log_track(h_, &log, first, count, accept_counts, &track), "runLogTrack");
+  }
   void synchronize() { check(uwvk_pose_synchronize(h_), "synchronize"); }
 
  private:

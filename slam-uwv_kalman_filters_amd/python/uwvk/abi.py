@@ -74,6 +74,11 @@ class PoseLog(C.Structure):  # uwvk_pose_log (device pointers)
                 ("host_flags", P)]
 
 
+class PoseTrack(C.Structure):  # uwvk_pose_track (device buffers; truth is a host pointer)
+    _fields_ = [("every", C.c_int64), ("capacity", C.c_int64), ("mean", P), ("variance", P), ("stats", P),
+                ("truth", P)]
+
+
 class VelLog(C.Structure):  # uwvk_vel_log (device pointers)
     _fields_ = [("epochs", C.c_int64), ("dt", D), ("flags", P), ("gyro", P), ("efforts", P),
                 ("dvl_index", P), ("dvl", P), ("dvl_cov", _arr(D, 9)),

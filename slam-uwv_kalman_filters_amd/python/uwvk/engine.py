@@ -45,6 +45,7 @@ SYMBOLS = [
     "uwvk_ipose_get_corrected_pose", "uwvk_ipose_get_state", "uwvk_ipose_get_status",
     "uwvk_pose_tail_chunks", "uwvk_pose_resident_slots", "uwvk_pose_epoch_qshape", "uwvk_pose_param_block", "uwvk_pose_pair_active", "uwvk_pose_timer_mark", "uwvk_pose_timer_elapsed",
     "uwvk_xcd_round_robin", "uwvk_synth_normal", "uwvk_synth_normal_at",
+    "uwvk_pose_track_records", "uwvk_pose_run_log_track",
 ]
 
 _LIB = None
@@ -99,6 +100,9 @@ def lib(path=None):
         L.uwvk_memcpy_h2d_on.argtypes = [VP, VP, C.c_size_t, VP]
         L.uwvk_memcpy_d2h_on.argtypes = [VP, VP, C.c_size_t, VP]
         L.uwvk_device_malloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(VP)]
+        if hasattr(L, "uwvk_pose_track_records"):  # an older ABI-3 build (UWVK_LIB A/B runs) has no track
+            L.uwvk_pose_track_records.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+            L.uwvk_pose_track_records.restype = C.c_int64
         _LIB = L
     return _LIB
 
@@ -126,6 +130,15 @@ class DeviceBuffer:
         _chk(lib().uwvk_device_malloc(device, self.nbytes, C.byref(self.ptr)), "device_malloc")
         if arr.nbytes:
             _chk(lib().uwvk_memcpy_h2d(self.ptr, arr.ctypes.data_as(VP), arr.nbytes), "memcpy_h2d")
+
+    @classmethod
+    def empty(cls, nbytes, device=0):
+        """An allocation of nbytes, contents undefined (outputs of device work)."""
+        b = cls.__new__(cls)
+        b.nbytes = max(int(nbytes), 16)
+        b.ptr = VP()
+        _chk(lib().uwvk_device_malloc(device, b.nbytes, C.byref(b.ptr)), "device_malloc")
+        return b
 
     def read(self, dtype, shape, stream=None):
         """Copy to the host after all queued device work (stream=None), or
@@ -335,6 +348,44 @@ class PoseUKFBatch:
         if sync:
             self.synchronize()
 
+    def track_records(self, first, count, every):
+        """Records run_log_track takes over epochs [first, first+count) (host only)."""
+        return int(self.L.uwvk_pose_track_records(first, count, every))
+
+    def run_log_track(self, dlog, every, first=0, count=None, accept_counts=None, mean=True, variance=True,
+                      stats=False, truth=None, sync=True, capacity=None):
+        """run_log with a record of all instances after every absolute epoch e
+        with (e + 1) % every == 0 (uwvk_pose_run_log_track): the means, the
+        diagonal of Sigma and / or the ensemble statistics against truth
+        ([records][store], host; None: ensemble_stats' None).  The records stay
+        in device memory, written on the handle's stream; the returned PoseTrack
+        reads them back.  capacity: records to allocate for (default: what the
+        range takes)."""
+        count = dlog.epochs - first if count is None else count
+        n = self.track_records(first, count, every)
+        cap = n if capacity is None else int(capacity)
+        s, nout = self.lay["store"], 3 * self.lay["store"] + 2
+        bufs = {}
+        for name, on, per in (("mean", mean, self.batch * s), ("variance", variance, self.batch * self.dof),
+                              ("stats", stats, nout)):
+            bufs[name] = DeviceBuffer.empty(cap * per * 8, self.device) if on else None
+        t = None
+        if stats and truth is not None:
+            t = _f64(truth)
+            if t.shape != (n, s):
+                raise ValueError("truth: %s, need one store-vector per record %s" % (t.shape, (n, s)))
+        tr = abi.PoseTrack()
+        tr.every, tr.capacity = int(every), cap
+        tr.mean, tr.variance, tr.stats = (bufs[k].ptr if bufs[k] else None for k in ("mean", "variance", "stats"))
+        tr.truth = _p(t)
+        _chk(self.L.uwvk_pose_run_log_track(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count),
+                                            accept_counts.ptr if accept_counts is not None else None,
+                                            C.byref(tr)), "run_log_track")
+        if sync:
+            self.synchronize()
+        epochs = (np.arange(first // every + 1, first // every + 1 + n, dtype=np.int64) * every - 1)
+        return PoseTrack(self, epochs, bufs)
+
     def ensemble_stats(self, truth=None, comm=None):
         """Ensemble statistics of this handle's instances; with an RcclComm,
         summed over every rank's shard by RCCL (uwvk_pose_ensemble_allreduce)."""
@@ -363,6 +414,38 @@ class PoseUKFBatch:
         ms = C.c_float(0)
         _chk(self.L.uwvk_pose_timer_elapsed(self.h, C.byref(ms)), "timer_elapsed")
         return ms.value
+
+
+class PoseTrack:
+    """The records of one PoseUKFBatch.run_log_track call, in device memory.
+    epochs: the absolute record epochs.  mean() / variance() / stats() copy to
+    the host, ordered on the filter's stream (None for an output not recorded)."""
+
+    def __init__(self, filt, epochs, bufs):
+        self.epochs = epochs
+        self.bufs = bufs
+        self._stream = filt.stream
+        self._shapes = dict(mean=(filt.batch, filt.lay["store"]), variance=(filt.batch, filt.dof),
+                            stats=(3 * filt.lay["store"] + 2,))
+
+    def _read(self, name):
+        b = self.bufs[name]
+        shape = (len(self.epochs),) + self._shapes[name]
+        if b is None or not len(self.epochs):
+            return None if b is None else np.empty(shape)
+        return b.read(np.float64, shape, self._stream)
+
+    def mean(self):
+        """[records][batch][store]"""
+        return self._read("mean")
+
+    def variance(self):
+        """[records][batch][dof]: the diagonal of Sigma"""
+        return self._read("variance")
+
+    def stats(self):
+        """[records][3*store+2]: ensemble_stats' layout"""
+        return self._read("stats")
 
 
 class DevicePoseLog:

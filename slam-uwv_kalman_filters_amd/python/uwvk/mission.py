@@ -145,6 +145,17 @@ def build_pose_log(batch, imu_t, gyro, acc, acc_cov, dvl=None, pressure=None, ad
     return log
 
 
+def replay(filt, log, every, truth=None):
+    """Run a mission log on an initialised PoseUKFBatch and return its
+    trajectory: after every `every`-th epoch the means and the diagonal of
+    Sigma of all instances (PoseUKFBatch.run_log_track), as numpy arrays.
+    truth ([records][store], one row per record epoch) adds the ensemble
+    statistics against it.  Returns dict(epochs, mean [records][batch][store],
+    variance [records][batch][dof], stats [records][3*store+2] or None)."""
+    track = filt.run_log_track(filt.upload_log(log), every, stats=truth is not None, truth=truth)
+    return dict(epochs=track.epochs, mean=track.mean(), variance=track.variance(), stats=track.stats())
+
+
 _ARRAYS = ("flags", "gyro", "acc", "acc_cov", "dvl_index", "dvl", "dvl_cov", "pressure_index", "pressure",
            "pressure_sensor_in_imu", "adcp_index", "adcp", "adcp_cell_weighting", "adcp_cov", "efforts_index",
            "efforts", "efforts_cov")

@@ -1,0 +1,85 @@
+// track_plan_test.cpp — the record cuts of uwvk_pose_run_log_track
+// (track_segments / track_records, csrc/uwvk_plan.hpp) on the CPU, over fixed
+// and seeded random (first, count, every): the segments tile the range in
+// order, each but possibly the last ends at a record epoch, their number is
+// the closed form, and a range split anywhere gives the two halves' records
+// one after the other.  Exit 0 = all checks hold.
+#include <cstdio>
+#include <random>
+
+#include "../../slam-uwv_kalman_filters_amd/csrc/uwvk_plan.hpp"
+
+using namespace uwvk;
+
+static int g_fail = 0;
+#define CHECK(c)                                                                                              \
+  do {                                                                                                        \
+    if (!(c)) {                                                                                               \
+      std::printf("FAIL %s:%d: %s (first %lld count %lld every %lld)\n", __FILE__, __LINE__, #c,              \
+                  (long long)first, (long long)count, (long long)every);                                      \
+      g_fail++;                                                                                               \
+    }                                                                                                         \
+  } while (0)
+
+// the record epochs of a range, from its segments
+static std::vector<int64_t> records(int64_t first, int64_t count, int64_t every) {
+  std::vector<int64_t> r;
+  for (const TrackSegment& s : track_segments(first, count, every))
+    if (s.record) r.push_back(s.first + s.count - 1);
+  return r;
+}
+
+static void check_case(int64_t first, int64_t count, int64_t every) {
+  const std::vector<TrackSegment> segs = track_segments(first, count, every);
+  int64_t e = first, nrec = 0;
+  for (size_t k = 0; k < segs.size(); k++) {
+    const TrackSegment& s = segs[k];
+    CHECK(s.first == e && s.count > 0);  // in order, no gap, no empty segment
+    e = s.first + s.count;
+    if (s.record) nrec++;
+    // every segment ends at a record epoch, the last possibly at the range's end
+    CHECK(s.record == (e % every == 0));
+    CHECK(s.record || k + 1 == segs.size());
+    // no record epoch inside a segment
+    for (int64_t q = s.first; q + 1 < e; q++) CHECK((q + 1) % every != 0);
+  }
+  CHECK(e == first + count);
+  CHECK(count > 0 || segs.empty());
+  CHECK(nrec == track_records(first, count, every));
+  CHECK(nrec == (first + count) / every - first / every);
+  // naive count
+  int64_t naive = 0;
+  for (int64_t q = first; q < first + count; q++) naive += (q + 1) % every == 0;
+  CHECK(nrec == naive);
+  // composition: the records of [first, cut) then [cut, first + count)
+  const std::vector<int64_t> whole = records(first, count, every);
+  for (int64_t cut = first; cut <= first + count; cut++) {
+    std::vector<int64_t> two = records(first, cut - first, every);
+    for (int64_t r : records(cut, first + count - cut, every)) two.push_back(r);
+    CHECK(two == whole);
+  }
+}
+
+int main() {
+  // every = 1, every > count, first not a multiple of every, count = 0, a range
+  // that ends on / one short of / one past a record epoch
+  const int64_t fixed[][3] = {{0, 120, 25}, {0, 10, 1},  {7, 10, 1},  {0, 5, 9},   {3, 5, 9},  {4, 5, 9},
+                              {13, 40, 7},  {13, 0, 7},  {0, 0, 1},   {70, 50, 25}, {0, 24, 25}, {0, 25, 25},
+                              {0, 26, 25},  {24, 1, 25}, {25, 1, 25}, {1999, 1, 1000}};
+  for (const auto& c : fixed) check_case(c[0], c[1], c[2]);
+  std::mt19937_64 rng(20240611);
+  for (int k = 0; k < 3000; k++) {
+    const int64_t first = (int64_t)(rng() % 300), count = (int64_t)(rng() % 200);
+    const int64_t every = 1 + (int64_t)(rng() % (k % 3 == 0 ? 8 : 260));
+    check_case(first, count, every);
+  }
+  // large epochs: no 32-bit arithmetic
+  {
+    const int64_t first = (int64_t(1) << 33) + 5, count = 1000, every = 300;
+    const std::vector<TrackSegment> segs = track_segments(first, count, every);
+    CHECK(!segs.empty() && segs.front().first == first && segs.back().first + segs.back().count == first + count);
+    CHECK((int64_t)records(first, count, every).size() == track_records(first, count, every));
+  }
+  std::printf("track plan: %s\n", g_fail ? "FAILED" : "ok");
+  return g_fail ? 1 : 0;
+}
