@@ -227,12 +227,16 @@ UWVK_DEV bool upper_half() { return lane_const<0xFFFFFFFF00000000ull>(); }
 // (r06) local lane J < 16 of each half by two DPP moves per dword:
 // row_newbcast:J (every 16-lane row takes its lane J), then row_bcast:15 into
 // rows 1 and 3 from rows 0 and 2 (row_mask 0xa; rows 0 and 2 keep their
-// value): 4 VALU per double instead of four v_readlane and two selects
+// value): 4 VALU per double instead of four v_readlane and two selects.
+// row_newbcast with all rows and banks gives every lane a source, so the old
+// value is never read: mov_dpp leaves it undefined, where update_dpp's
+// explicit 0 cost a v_mov_b32 per dword before the DPP move (as uwvk_vel.hip
+// vdpp).  The second stage's row mask keeps rows 0 and 2: its old value is read.
 template <int J>
 UWVK_DEV double hbc(double v) {
   static_assert(J >= 0 && J < 16, "row_newbcast lane");
-  int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x150 + J, 0xf, 0xf, false);
-  int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x150 + J, 0xf, 0xf, false);
+  int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x150 + J, 0xf, 0xf, false);
+  int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x150 + J, 0xf, 0xf, false);
   lo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xa, 0xf, false);
   hi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xa, 0xf, false);
   return __hiloint2double(hi, lo);

@@ -90,6 +90,23 @@ UWVK_DEV int pd_pidx(int e) {
   return (I * (I + 1)) / 2 + J;
 }
 UWVK_DEV constexpr int pd_diag53(int t) { return ((19 + t) * (20 + t)) / 2 + 19 + t; }
+// pd_pidx of every flat slot e = l + 32 t of a local lane, once per wave: the
+// map depends on the lane and the slot only, and load_pair / store_pair paid
+// its sqrtf, fix-ups and products for 11 slots per lane in every work unit
+// (~750 VALU each).  16-bit entries (the largest index is 1,430) in LDS, one
+// table for both halves; the units' loads and stores read their 11 indices
+// from it (not kept in VGPRs across the epoch loop: the kernel is at its
+// register limit).  Slots past the triangle hold 0 and are never used.
+constexpr int kPdTab = PG<26>::NSLOT * kLanes;
+static_assert(PG<53>::NP <= 65536, "16-bit table entries");
+UWVK_DEV void pd_tab_fill(unsigned short* tab, int l) {
+#pragma unroll
+  for (int t = 0; t < PG<26>::NSLOT; t++) {
+    const int e = l + kLanes * t;
+    tab[e] = (unsigned short)(e < PG<26>::NP ? pd_pidx(e) : 0);
+  }
+  psync();
+}
 
 // per-lane process-model constants of the 26-DOF layout (uwvk_psp_k.hip
 // lane_proc<26>), s = the local lane
@@ -140,7 +157,8 @@ UWVK_DEV void par_epoch(double* px, int t, double dt, const ParLane& p) {
 
 // the pair's state through the 26-DOF layout: instance inst's Sigma~ subset,
 // 27 stored means, the parameters' diagonal and means (local lanes, 32 per instance)
-UWVK_DEV void load_pair(PspSmem<26>& sm, double* px, const PoseBufs& b, int64_t inst, int l) {
+UWVK_DEV void load_pair(PspSmem<26>& sm, double* px, const unsigned short* tab, const PoseBufs& b, int64_t inst,
+                        int l) {
   using G = PG<26>;
   const double* gs = b.sigma + inst * (int64_t)PG<53>::NP;
   const double* gm = b.mu + inst * (int64_t)Lay<53>::store;
@@ -148,7 +166,7 @@ UWVK_DEV void load_pair(PspSmem<26>& sm, double* px, const PoseBufs& b, int64_t 
 #pragma unroll
   for (int t = 0; t < G::NSLOT; t++) {
     const int e = l + kLanes * t;
-    v[t] = e < G::NP ? gs[pd_pidx(e)] : 0.0;
+    v[t] = e < G::NP ? gs[tab[e]] : 0.0;
   }
   const double m = l < Lay<26>::store ? gm[pd_store(l)] : 0.0;
   const bool pl = l < kPdN;
@@ -165,7 +183,8 @@ UWVK_DEV void load_pair(PspSmem<26>& sm, double* px, const PoseBufs& b, int64_t 
   }
   psync();
 }
-UWVK_DEV void store_pair(const PspSmem<26>& sm, const double* px, const PoseBufs& b, int64_t inst, int l) {
+UWVK_DEV void store_pair(const PspSmem<26>& sm, const double* px, const unsigned short* tab, const PoseBufs& b,
+                         int64_t inst, int l) {
   using G = PG<26>;
   double* gs = b.sigma + inst * (int64_t)PG<53>::NP;
   double* gm = b.mu + inst * (int64_t)Lay<53>::store;
@@ -179,7 +198,7 @@ UWVK_DEV void store_pair(const PspSmem<26>& sm, const double* px, const PoseBufs
 #pragma unroll
   for (int t = 0; t < G::NSLOT; t++) {
     const int e = l + kLanes * t;
-    if (e < G::NP) gs[pd_pidx(e)] = v[t];
+    if (e < G::NP) gs[tab[e]] = v[t];
   }
   if (l < Lay<26>::store) gm[pd_store(l)] = m;
   if (pl) {
@@ -259,6 +278,7 @@ template <int SR, int EVS, int PD>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PSP_PAIR_WAVES, PSP_PAIR_WAVES)))
 void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
   __shared__ PspSmemPD<26> smx[2];
+  __shared__ unsigned short pdx[PD ? kPdTab : 1];  // the PD index map (pd_tab_fill)
   const int h = half();
   PspSmem<26>& sm = smx[h];
   double* const px = smx[h].pS;
@@ -266,6 +286,7 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
   const int64_t B = b.batch;
   const uint32_t grid = gridDim.x;
   uint32_t u = blockIdx.x;
+  if constexpr (PD) pd_tab_fill(pdx, olane());
 #pragma unroll 1
   while (u < ea.units) {
     const PUnit tu = ticket_unit(ea, u);
@@ -305,7 +326,7 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
       }
     };
     if (e_end > e_begin) fetch(e_begin);
-    if constexpr (PD) load_pair(sm, px, b, inst, l);
+    if constexpr (PD) load_pair(sm, px, pdx, b, inst, l);
     else load_pair26(sm, b, inst, l);
     double ds = 1.0, ids = 1.0;  // time scale of the 26-DOF layout's Markov DOFs
     if (tu.chunk > 0) {
@@ -387,7 +408,7 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
     } else {
       psp_fold<26, 0>(sm, ds, ids);
     }
-    if constexpr (PD) store_pair(sm, px, b, inst, l);
+    if constexpr (PD) store_pair(sm, px, pdx, b, inst, l);
     else store_pair26(sm, b, inst, l);
     if (hand) tail_signal(ea, tn.tslot, tn.chunk);
     u = un;
