@@ -299,9 +299,23 @@ struct Stamper {
   UWVK_DEV void mark(int) {}
 };
 #endif
+// -DUWVK_PHASE_MARKS (diagnostic, tools/isa_phases.py pair): every stamp site
+// becomes an assembler comment between two scheduling barriers, so that the
+// static instruction mix of a kernel that carries no Stamper (the pair kernel)
+// can be split by phase; no instruction is added.
+#ifdef UWVK_PHASE_MARKS
+#define UWVK_STAMP(ph)                           \
+  do {                                           \
+    (void)st;                                    \
+    __builtin_amdgcn_sched_barrier(0);           \
+    asm volatile("; uwvk_phase %0" ::"n"(ph));   \
+    __builtin_amdgcn_sched_barrier(0);           \
+  } while (0)
+#else
 #define UWVK_STAMP(ph) \
   do {                 \
     if (st) st->mark(ph); \
   } while (0)
+#endif
 
 }  // namespace uwvk

@@ -38,6 +38,7 @@
 #include <cstddef>
 
 #include "uwvk_pose_dev.hpp"
+#include "uwvk_tiles.hpp"
 
 // r05: the compile-time A/B knobs of rounds 1-4 (PSP_*: lane-limited wave
 // sums, LDS broadcasts, the three rank-M MFMA forms, lane masks, SGPR series
@@ -52,8 +53,9 @@
 // l & 31 (olane), builds its lane masks for the 32 local lanes of both halves
 // (lane_mask / LANE_IN), reads a value of local lane j of its own half with
 // hread (two readlanes and a select instead of one readlane), sums within a
-// half (wave_sum_dpp), and runs Sigma~ -= C~ K~^T as a lane-per-row FMA sweep
-// (rankm_rows: one MFMA tile spans all 64 lanes).  The code is compiled there
+// half (wave_sum_dpp), and runs Sigma~ -= C~ K~^T as an FMA chain per entry on
+// 4x4 register tiles (rankm_tiles: one MFMA tile spans all 64 lanes) and the
+// partial Choleskys two columns per LDS round trip (pchol_step2_lds).  The code is compiled there
 // under PSP_NS = psp2; the single-instance kernels (uwvk_psp_k.hip) are
 // PSP_PAIR 0, namespace psp.
 #ifndef PSP_PAIR
@@ -564,6 +566,67 @@ UWVK_DEV void pchol_step_lds(double (&a)[K], int r, bool& ok, double* col, doubl
   }
 }
 
+#if PSP_PAIR
+// Two columns per LDS round trip: columns J and J + 1 are finished from the
+// 2x2 pivot block (L[J+1][J] and the second pivot by per-half DPP broadcasts
+// from lane J + 1 < 16), every lane writes the pair (L[r][J], L[r][J+1]) as one
+// 16-byte slot, and the trailing update reads column pairs as aligned
+// ds_read_b128.  Each entry sees the operations of two single steps in their
+// order (a[c] -= a[J] L[c][J], then a[c] -= a[J+1] L[c][J+1]), so the factor is
+// bitwise the single-column one.  An odd K ends with a single column.  col2 is
+// 16-byte aligned.
+// Every operation is written out (no contraction left to the compiler).  In
+// the first pair the panel's scaling is still pending for the columns c >= 2:
+// a[c] holds Sigma~[r][c] and f[c] its scale, and the first subtraction is
+// fma(f[c], a[c], -(a[0] L[c][0])) -- the product rounded, the scaling fused --
+// which is how the single-column form's first step was compiled (the scaled
+// entry's only use); column 1 (used twice there) is scaled on its own.
+template <int K, int J>
+UWVK_DEV void pchol_step2_lds(double (&a)[K], const double (&f)[K], int r, bool& ok, double* col2, double piv) {
+#pragma clang fp contract(off)
+  if constexpr (J + 1 == K) {  // the last column of an odd K: nothing to broadcast
+    ok = ok && (piv > 0.0);
+    const double inv = rsqrt_f64(piv);
+    a[J] = LANE_IF(r, r >= J) ? a[J] * inv : 0.0;
+  } else if constexpr (J + 1 < K) {
+    static_assert(J + 1 < 16, "hbc lanes");
+    ok = ok && (piv > 0.0);
+    const double inv0 = rsqrt_f64(piv);
+    a[J] = LANE_IF(r, r >= J) ? a[J] * inv0 : 0.0;
+    // column J + 1 from the pivot block: L[J+1][J] is lane J + 1's a[J]
+    a[J + 1] = fma(-a[J], hread(a[J], J + 1), a[J + 1]);
+    const double piv1 = hread(a[J + 1], J + 1);
+    ok = ok && (piv1 > 0.0);
+    const double inv1 = rsqrt_f64(piv1);
+    a[J + 1] = LANE_IF(r, r >= J + 1) ? a[J + 1] * inv1 : 0.0;
+    double pnext = 0.0;
+    if constexpr (J + 2 < K) {
+      // look-ahead: pivot J + 2 from lane J + 2's own registers
+      {
+        const double t = J == 0 ? fma(f[J + 2], a[J + 2], -(a[J] * a[J])) : fma(-a[J], a[J], a[J + 2]);
+        pnext = hread(fma(-a[J + 1], a[J + 1], t), J + 2);
+      }
+      static_assert(2 * kLanes + 1 <= 115, "column pair slots (PG::STG)");
+      double* const c2 = static_cast<double*>(__builtin_assume_aligned(col2, 16));
+      double* const w = static_cast<double*>(__builtin_assume_aligned(c2 + 2 * (r & (kLanes - 1)), 16));
+      w[0] = a[J];
+      w[1] = a[J + 1];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int c = J + 2; c < K; c++) {
+        const double t = J == 0 ? fma(f[c], a[c], -(a[J] * c2[2 * c])) : fma(-a[J], c2[2 * c], a[c]);
+        a[c] = fma(-a[J + 1], c2[2 * c + 1], t);
+      }
+#pragma unroll
+      for (int c = J + 2; c < K; c++) asm volatile("" : "+v"(a[c]));
+    }
+    pchol_step2_lds<K, J + 2>(a, f, r, ok, col2, pnext);
+  }
+}
+#endif
+
 // staged rows of L_a start here inside sm.stg; the Cholesky column buffer is
 // folded into the last staged row (pchol_step_lds)
 constexpr int STG_ROWS = 0;
@@ -577,8 +640,18 @@ UWVK_DEV bool pchol(const double* S, int r, double (&a)[K], double dl, double* s
   // a later (finite) entry of Sigma~, which the column steps never use (they
   // zero L[r][c] for r < c before it is read)
   const double* Sr = S + rr * (rr + 1) / 2;
+#if PSP_PAIR
+  static_assert(K >= 2, "column pairs");
+  double f[K];  // the entries' scales: columns >= 2 are scaled in the first pair's update
+#pragma unroll
+  for (int c = 0; c < K; c++) {
+    f[c] = scaled_dof(c) ? dl * hread(dl, c) : dl;
+    a[c] = c < 2 ? Sr[c] * f[c] : Sr[c];
+  }
+#else
 #pragma unroll
   for (int c = 0; c < K; c++) a[c] = Sr[c] * (scaled_dof(c) ? dl * hread(dl, c) : dl);
+#endif
   bool ok = true;
   // the staged-row slot of lane r is its rank among the staged rows (the row
   // list is ascending): the set bits of the constant row mask below the lane,
@@ -589,12 +662,17 @@ UWVK_DEV bool pchol(const double* S, int r, double (&a)[K], double dl, double* s
   if constexpr (PSP_PAIR) q -= upper_half() ? __builtin_popcount((unsigned)rm) : 0;  // the lower half's rows
   static_assert(RL::NR >= 1 && STG_ROWS + RL::NR * K <= 115, "staging area (PG::STG)");
   const double p0 = hread(a[0], 0);
-  const double inv0 = rsqrt_f64(p0);
-  double chk = fma(inv0, 0.0, 0.0);
   // the column buffer anywhere in the (not yet written) rows area; the rows are
   // staged after the last step, one lane-addressed run of K stores per row
   // lane, instead of one masked store (and its address product) per step
+#if PSP_PAIR
+  // (the column pairs' slots from the first 16-byte boundary of stg)
+  pchol_step2_lds<K, 0>(a, f, r, ok, stg + ((PG<DOF>::NP + Lay<DOF>::store) & 1), p0);
+#else
+  const double inv0 = rsqrt_f64(p0);
+  double chk = fma(inv0, 0.0, 0.0);
   pchol_step_lds<K, 0>(a, r, ok, stg + STG_ROWS, stg + STG_ROWS, q, p0, inv0, chk);
+#endif
   if (LANE_IN(rows_mask<RL>())) {  // q >= 0
     double* rp = stg + STG_ROWS + q * K;
 #pragma unroll
@@ -1443,48 +1521,109 @@ UWVK_DEV void rankm_mfma_o(double* S, double* stg, const double (&Ct)[M], const 
 }
 
 #else
-// PSP_PAIR: Sigma~ -= C~ K~^T as a lane-per-row sweep (one v_mfma_f64_16x16x4
-// tile spans all 64 lanes, i.e. both instances): lane r holds C~_r and K~_r;
-// K~ of every row is staged in the instance's stg and read back as broadcasts;
-// row r's entries go in blocks of RB columns, each block's loads before its
-// stores; only the entries on or below the diagonal are stored (lane masks)
-// the rows r of column j's entries: j <= r < DOF (local lanes of either half)
+// PSP_PAIR: Sigma~ -= C~ K~^T on 4x4 register tiles (one v_mfma_f64_16x16x4
+// tile spans all 64 lanes, i.e. both instances), one tile of the block
+// triangle per local lane (uwvk_tiles.hpp: 26 DOFs are 28 tiles on 32 lanes).
+// Lane t holds the 16 entries of tile (rb, cb), C~ of its 4 rows and K~ of its
+// 4 columns, and runs the FMA chain s = fma(-C~_i[k], K~_j[k], s), k = 0 ..
+// M - 1, on each entry.  (r06 - r07 ran one lane per row over 26 column steps:
+// the same chain per entry, so the results are bitwise those; half of its
+// lane-slots lay above the diagonal, every step had its own Sigma~ access,
+// K~_j broadcast and EXEC mask.  Here: 16 M instead of 26 M FMAs, a tile row's
+// four contiguous entries per LDS access, the operands as 4 M contiguous
+// doubles, one EXEC mask per group of tile positions; profiles/r08/.)
+// K~ and C~ go through the staging area one after the other (both at once are
+// 2 * 32 M doubles, more than PG::STG): every local lane writes its M values
+// to slot l (rows >= DOF hold values that the last row block's lanes load and
+// never store).  Stores: tiles::stores -- lanes without a tile (>= 28)
+// nothing, diagonal tiles v <= u only, rows >= DOF never; loads run past the
+// triangle (above the diagonal, rows 26 / 27) and stay inside PspSmem.
 template <int DOF>
-UWVK_DEV constexpr unsigned long long rankm_col_mask(int j) {
-  unsigned long long m = 0;
-  for (int l = 0; l < 64; l++)
-    if (l >= j && l < DOF) m |= 1ull << l;
-  return m;
+struct TileStoreGroups {
+  unsigned long long m[16];  // store mask of tile position p = 4 u + v (local lanes 0..31)
+  bool lead[16];             // the first position with this mask
+  unsigned long long rbm[3], cbm[3];  // lanes whose row / column block has bit b set
+};
+template <int DOF>
+UWVK_DEV constexpr TileStoreGroups<DOF> tile_store_groups() {
+  TileStoreGroups<DOF> g{};
+  for (int p = 0; p < 16; p++) {
+    g.m[p] = tiles::store_mask(DOF, p / 4, p % 4);
+    g.lead[p] = g.m[p] != 0;
+    for (int q = 0; q < p; q++)
+      if (g.m[q] == g.m[p]) g.lead[p] = false;
+  }
+  for (int b = 0; b < 3; b++) {
+    g.rbm[b] = tiles::block_bit_mask(DOF, false, b);
+    g.cbm[b] = tiles::block_bit_mask(DOF, true, b);
+  }
+  return g;
 }
 template <int DOF, int M>
-UWVK_DEV void rankm_rows(double* S, double* stg, const double (&Ct)[M], const double (&Kt)[M], int l) {
-  static_assert(DOF * M <= PG<DOF>::STG, "K~ rows (PG::STG)");
-  constexpr int RB = 4;
-  if (l < DOF) {
+UWVK_DEV void rankm_tiles(PspSmem<DOF>& sm, const double (&Ct)[M], const double (&Kt)[M], int l) {
+  constexpr int TB = tiles::TB;
+  static_assert(TB == 4 && tiles::num_tiles(DOF) <= kLanes && tiles::block_bits(DOF) <= 3, "one 4x4 tile per local lane");
+  // the operand slots start on a 16-byte boundary (PspSmem is 16-byte aligned,
+  // stg follows NP + store doubles), so that a tile's 4 M operand doubles are
+  // aligned ds_read_b128 pairs
+  constexpr int ST0 = (PG<DOF>::NP + Lay<DOF>::store) & 1;
+  static_assert(ST0 + kLanes * M <= PG<DOF>::STG, "one operand's slots (PG::STG)");
+  static_assert((TB * M) % 2 == 0, "a tile's operands start aligned");
+  static_assert(tiles::max_load_index(DOF) < (int)(sizeof(PspSmem<DOF>) / sizeof(double)),
+                "tile loads past the triangle stay in PspSmem");
+  constexpr TileStoreGroups<DOF> G = tile_store_groups<DOF>();
+  double* const st = sm.stg + ST0;
+  double* const fl = flat(sm);
+  // the lane's block numbers from constant lane masks (scalar constants)
+  int rb = 0, cb = 0;
 #pragma unroll
-    for (int k = 0; k < M; k++) stg[l * M + k] = Kt[k];
+  for (int b = 0; b < 3; b++) {
+    if (G.rbm[b]) rb |= LANE_IN(G.rbm[b]) ? (1 << b) : 0;
+    if (G.cbm[b]) cb |= LANE_IN(G.cbm[b]) ? (1 << b) : 0;
   }
+#pragma unroll
+  for (int k = 0; k < M; k++) st[l * M + k] = Kt[k];
   wsync();
-  const int lc = l < DOF ? l : DOF - 1;
-  const int b0 = (lc * (lc + 1)) >> 1;
-  // (r06) entry (r, j) loaded from S[T(r) + j] for every lane (j > r reads a
-  // later entry of the triangle: T(r) + j <= T(DOF - 1) + DOF - 1 < NP) and
-  // stored under the constant lane mask {l : j <= l < DOF} (an EXEC mask by
-  // scalar instructions), instead of two address selects per entry to a
-  // throw-away slot: +1.5% at 200 epochs (profiles/r06/r06q/)
+  double kt[TB][M], ct[TB][M];
+  {
+    const double* kp = static_cast<const double*>(__builtin_assume_aligned(st + cb * (TB * M), 16));
 #pragma unroll
-  for (int j0 = 0; j0 < DOF; j0 += RB) {
-    double sv[RB];
+    for (int v = 0; v < TB; v++)
 #pragma unroll
-    for (int u = 0; u < RB; u++)
-      if (j0 + u < DOF) sv[u] = S[b0 + j0 + u];
+      for (int k = 0; k < M; k++) kt[v][k] = kp[v * M + k];
+  }
+  // the tile: row u's four entries from T(4 rb + u) + 4 cb
+  const int i0 = TB * rb;
+  const int e0 = ((i0 * (i0 + 1)) >> 1) + TB * cb;
+  double sv[TB][TB];
 #pragma unroll
-    for (int u = 0; u < RB; u++) {
-      if (j0 + u >= DOF) continue;
-      double s2 = sv[u];
+  for (int u = 0; u < TB; u++)
 #pragma unroll
-      for (int k = 0; k < M; k++) s2 = fma(-Ct[k], stg[(j0 + u) * M + k], s2);
-      if (LANE_IN(rankm_col_mask<DOF>(j0 + u))) S[b0 + j0 + u] = s2;
+    for (int v = 0; v < TB; v++) sv[u][v] = fl[e0 + u * i0 + tiles::tri(u) + v];
+  wsync();  // every lane's K~ reads before the C~ writes
+#pragma unroll
+  for (int k = 0; k < M; k++) st[l * M + k] = Ct[k];
+  wsync();
+  {
+    const double* cp = static_cast<const double*>(__builtin_assume_aligned(st + rb * (TB * M), 16));
+#pragma unroll
+    for (int u = 0; u < TB; u++)
+#pragma unroll
+      for (int k = 0; k < M; k++) ct[u][k] = cp[u * M + k];
+  }
+#pragma unroll
+  for (int u = 0; u < TB; u++)
+#pragma unroll
+    for (int v = 0; v < TB; v++)
+#pragma unroll
+      for (int k = 0; k < M; k++) sv[u][v] = fma(-ct[u][k], kt[v][k], sv[u][v]);
+#pragma unroll
+  for (int p = 0; p < 16; p++) {
+    if (!G.lead[p]) continue;
+    if (LANE_IN(G.m[p])) {
+#pragma unroll
+      for (int q = p; q < 16; q++)
+        if (G.m[q] == G.m[p]) fl[e0 + (q / 4) * i0 + tiles::tri(q / 4) + q % 4] = sv[q / 4][q % 4];
     }
   }
   wsync();  // stg is rewritten next
@@ -1804,8 +1943,8 @@ UWVK_DEV bool psp_update(PspSmem<DOF>& sm, const double (&z)[HM::M], const doubl
   const bool accept = gate == 0 ? true : !(d2 > kD2P95);
   if (!accept) return false;
   PSP_PHASE(33);
-  // Sigma -= C K^T: row sweep (rankm_rows), lane = column j holds K_j, C_i is
-  // an LDS broadcast; each block's loads precede its stores.  delta = K nu (lane r).
+  // Sigma -= C K^T (pair: rankm_tiles, one 4x4 tile per lane; else the MFMA
+  // form).  delta = K nu (lane r).
   psync();
   double dl = 0.0;  // delta = K nu, lane r
 #pragma unroll
@@ -1819,7 +1958,7 @@ UWVK_DEV bool psp_update(PspSmem<DOF>& sm, const double (&z)[HM::M], const doubl
   }
   psync();
 #if PSP_PAIR
-  rankm_rows<DOF, M>(sm.S, sm.stg, Ct, Kt, l);
+  rankm_tiles<DOF, M>(sm, Ct, Kt, l);
 #else
   if constexpr (M <= 3) {
     rankm_mfma_o<DOF, M>(sm.S, sm.stg, Ct, Kt, l);

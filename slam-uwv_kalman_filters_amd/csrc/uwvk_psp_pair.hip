@@ -8,8 +8,9 @@
 // own PspSmemPD: one wave instruction serves both instances.  The PSP routines
 // are the same source compiled with PSP_PAIR = 1 (namespace psp2): lane masks
 // on the 32 local lanes of both halves, per-half broadcasts (hread) and sums,
-// and Sigma~ -= C~ K~^T as a lane-per-row FMA sweep instead of the MFMA tile
-// (one v_mfma_f64_16x16x4 spans 64 lanes).  A work unit is a PAIR of
+// Sigma~ -= C~ K~^T as FMA chains on 4x4 register tiles, one tile per lane
+// (rankm_tiles), instead of the MFMA tile (one v_mfma_f64_16x16x4 spans 64
+// lanes), and the partial Choleskys two columns per LDS round trip.  A work unit is a PAIR of
 // instances (2u, 2u + 1) over an epoch range: the persistent scheduler, tail
 // chunks and their hand-offs work on pair units exactly as k_psp_epoch_p on
 // instances.  The arithmetic per instance is the single kernel's except for the
