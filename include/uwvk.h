@@ -50,7 +50,10 @@ extern "C" {
  *      the instances' UWVK_ST_SCHEDULE bit: the next uwvk_pose_synchronize
  *      or uwvk_pose_run_log on the handle after the launch has completed
  *      returns UWVK_ESCHEDULE (once); new option UWVK_OPT_WAIT_BOUND;
- *      UWVK_OPT_PERSIST defaults to 1 (no dispatch-order assumption). */
+ *      UWVK_OPT_PERSIST defaults to 1 (no dispatch-order assumption);
+ *      added within 3, purely additive (no existing struct, flag or entry
+ *      point changed): uwvk_pose_fixes, UWVK_FIX_*, uwvk_pose_run_log_fixes,
+ *      uwvk_schedule_fixes. */
 #define UWVK_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
@@ -421,6 +424,54 @@ int64_t uwvk_pose_track_records(int64_t first, int64_t count, int64_t every);
 uwvk_status uwvk_pose_run_log_track(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
                                     uint32_t* accept_counts, const uwvk_pose_track* track);
 
+/* Position fixes as events of a device-resident run: XY (USBL / LBL,
+ * integrateMeasurement(XY_Position), PoseUKF.cpp:506-512), Z (PoseUKF.cpp:498-504)
+ * and GPS (integrateMeasurement(GeographicPosition, gps_in_body),
+ * PoseUKF.cpp:567-579, d2p95 gate).  They have their own per-epoch flags (the
+ * UWVK_EV_* bits and uwvk_pose_log are not extended); flags and row indices are
+ * HOST arrays (a fix epoch ends a launch and the host plans it), the payloads
+ * DEVICE arrays.  Order within an epoch: predict, Acceleration, DVL, pressure,
+ * ADCP cells, BodyEfforts, then XY, Z, Geographic; a track record of that epoch
+ * is taken after the fixes. */
+#define UWVK_FIX_XY  0x1u
+#define UWVK_FIX_Z   0x2u
+#define UWVK_FIX_GEO 0x4u
+typedef struct uwvk_pose_fixes {
+  const uint32_t* host_flags;  /* HOST [log->epochs] UWVK_FIX_* per epoch, required */
+  const int32_t* xy_index;     /* HOST [epochs] row into xy where UWVK_FIX_XY (NULL if never) */
+  const double* xy;            /* DEVICE [n_xy][batch][2] */
+  int64_t n_xy;
+  double xy_cov[4];            /* host values, shared */
+  const int32_t* z_index;      /* HOST [epochs] */
+  const double* z;             /* DEVICE [n_z][batch] */
+  int64_t n_z;
+  double z_cov;
+  const int32_t* geo_index;    /* HOST [epochs] */
+  const double* geo;           /* DEVICE [n_geo][batch][2] lat, lon (rad) */
+  int64_t n_geo;
+  double geo_cov[4];
+  double gps_in_body[3];
+  uint32_t* accept_counts;     /* DEVICE [batch][3] XY, Z, GEO accepted (nullable) */
+} uwvk_pose_fixes;
+
+/* uwvk_pose_run_log_track with fixes.  The result is bitwise that of
+ * uwvk_pose_run_log on each segment between fix epochs with uwvk_pose_update_xy,
+ * _z and _geographic (in that order, on the same rows, with the shared
+ * covariances and gps_in_body of `fixes`) at each cut: the final state, every
+ * track record, accept_counts, the per-instance status and the kernel choice of
+ * later calls (a fix does not couple the parameter block).  A non-finite fix
+ * value is skipped for that instance and kind (UWVK_ST_NAN), as the log's other
+ * sensors are; the call does not fail.
+ * fixes == NULL is uwvk_pose_run_log_track (track == NULL too: uwvk_pose_run_log).
+ * UWVK_EINVAL, with nothing queued and the state untouched, checked over
+ * [first, first + count) before the first launch: host_flags NULL; a flag bit
+ * outside UWVK_FIX_*; a flagged kind whose index or payload pointer is NULL; an
+ * index outside [0, n_kind) at a flagged epoch.  Otherwise the errors of
+ * uwvk_pose_run_log_track. */
+uwvk_status uwvk_pose_run_log_fixes(uwvk_pose* h, const uwvk_pose_log* log, const uwvk_pose_fixes* fixes,
+                                    int64_t first, int64_t count, uint32_t* accept_counts,
+                                    const uwvk_pose_track* track /* nullable */);
+
 /* Ensemble statistics over the batch (for Monte-Carlo runs):
  * out[0..store)        = sum_i x_i (orientation quaternion summed componentwise)
  * out[store..2*store)  = sum_i x_i^2
@@ -608,6 +659,19 @@ typedef struct uwvk_schedule {
  * UWVK_EINVAL); time_epsilon: stamp slack in seconds. */
 uwvk_status uwvk_schedule_streams(const uwvk_stream_times* in, double dt_tolerance, double time_epsilon,
                                   uwvk_schedule* out);
+
+/* The position-fix stamps of a recording placed on the epochs of its IMU
+ * stream (imu[n_imu], ascending), for uwvk_pose_fixes: the release rule, the
+ * per-sensor queue and the drop counting of uwvk_schedule_streams.  flags
+ * [n_imu] receives UWVK_FIX_* (overwritten); each index array [n_imu] the row
+ * of the sample integrated at that epoch, -1 = none (NULL allowed when that
+ * sensor has no samples); rows are the kept samples in order.  kept / dropped:
+ * XY, Z, GEO.  Stamps ascending per sensor, else UWVK_EINVAL. */
+uwvk_status uwvk_schedule_fixes(const double* imu, int64_t n_imu,
+                                const double* xy_t, int64_t n_xy, const double* z_t, int64_t n_z,
+                                const double* geo_t, int64_t n_geo, double time_epsilon,
+                                uint32_t* flags, int32_t* xy_index, int32_t* z_index, int32_t* geo_index,
+                                int64_t kept[3], int64_t dropped[3]);
 
 /* ADCP cell weighting for integrateMeasurement(WaterVelocityMeasurement,
  * cell_weighting) (PoseUKF.cpp:133-151,604-611) from cell_size and

@@ -2,7 +2,8 @@
 // integers and host arrays (plain C++17, no HIP): which epoch kernel a handle
 // runs, how a log range splits into launches, the grid and tail layout of one
 // launch, and the process-noise tables.  uwvk_pose.hip does the copies and the
-// launches; tests/cpp/plan_test.cpp checks this file on the CPU.
+// launches; tests/cpp/plan_test.cpp, track_plan_test.cpp and fix_plan_test.cpp
+// check this file on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -149,10 +150,10 @@ inline bool runs_pair(const EpochFacts& f) {
   return f.dof == 26 ? f.q_simple : runs_pd(f);
 }
 
-enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EFFORTS };
+enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EFFORTS, FIX };
 struct Launch {
   LaunchKind kind;
-  int64_t first, count;  // absolute epochs [first, first + count); EFFORTS: the one epoch
+  int64_t first, count;  // absolute epochs [first, first + count); EFFORTS, FIX: the one epoch
   int pd;                // EPOCH_*: the parameter-decoupled form
   int vo;                // EFFORTS: the velocity-only form (UWVK_EV_EFFORTS_VELOCITY_ONLY)
   uint32_t ev_any;       // the OR of the epochs' flags (the kernel instantiation)
@@ -242,6 +243,35 @@ inline std::vector<TrackSegment> track_segments(int64_t first, int64_t count, in
     e = stop;
   }
   return s;
+}
+
+// Position fixes (uwvk_pose_run_log_fixes): [first, first + count) is cut after
+// every epoch whose fix flags (UWVK_FIX_*) are non-zero.  Each piece is planned
+// by plan_epochs on its own, pdec carried from piece to piece, so a run with
+// fixes is the runs of its pieces, launch for launch; a piece that ends in a
+// fix epoch is followed by one FIX launch of that epoch (count 1, ev_any the
+// UWVK_FIX_* mask), after the piece's EFFORTS launch if the epoch has one (the
+// fixes are the last updates of an epoch).  A fix is linear in the position
+// rows and leaves the parameter block decoupled: pd / pair go on after it.
+// fix_flags: those of epochs first .. first + count - 1, or null (none): then,
+// and with all of them zero, the plan is plan_epochs' plan.
+inline EpochPlan plan_fix_epochs(const uint32_t* host_flags, const uint32_t* fix_flags, int64_t first, int64_t count,
+                                 EpochFacts f) {
+  EpochPlan p;
+  p.pdec = f.pdec;
+  const int64_t end = first + count;
+  for (int64_t e = first; e < end;) {
+    int64_t stop = e;
+    while (stop < end && !(fix_flags && fix_flags[stop - first])) stop++;
+    const bool fix = stop < end;
+    if (fix) stop++;  // the piece includes its fix epoch
+    const EpochPlan piece = plan_epochs(host_flags + (e - first), e, stop - e, f);
+    p.launches.insert(p.launches.end(), piece.launches.begin(), piece.launches.end());
+    f.pdec = p.pdec = piece.pdec;
+    if (fix) p.launches.push_back({FIX, stop - 1, 1, 0, 0, fix_flags[stop - 1 - first]});
+    e = stop;
+  }
+  return p;
 }
 
 // Last-generation spreading.  Blocks of one XCD are dispatched in order to

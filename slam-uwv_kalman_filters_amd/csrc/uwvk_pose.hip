@@ -605,21 +605,59 @@ static double* stats_partials(const uwvk_pose* h) { return h->d_scratch + 256 + 
 // ea: the log's arguments (a copy per call: the launch fields start cleared);
 // hf: the host flags of these epochs (PSP path); sh: the handle's PoseShared
 // after upload_shared.
+// fx: the position fixes of uwvk_pose_run_log_fixes (validated over the call's
+// range by fixes_valid), or null.
 static uwvk_status run_epochs(uwvk_pose* h, const PoseBufs& b, const PoseShared& sh, EpochArgs ea, const uint32_t* hf,
-                              int64_t first, int64_t count) {
+                              int64_t first, int64_t count, const uwvk_pose_fixes* fx) {
+  const int64_t B = h->batch;
   if (use_dense(h)) {  // literal kernels: one fused launch per epoch
     for (int64_t e = first; e < first + count; e++) {
       ea.first = e;
       ea.count = 1;
       HIPCHK(launch_pose_epoch(h->dof, h->stream, b, sh, ea));
+      const uint32_t kinds = fx ? fx->host_flags[e] : 0u;
+      if (!kinds) continue;
+      // the epoch's fixes: the literal k_pose_update per kind, on the log's device rows
+      auto fix = [&](int kind, int slot, int m, const double* row, const double* cov, const double* v3) {
+        MeasArgs ma{};
+        ma.mu = row;
+        std::memcpy(ma.shared_cov, cov, (size_t)m * m * 8);
+        if (v3)
+          for (int k = 0; k < 3; k++) ma.v3[k] = v3[k];
+        ma.accepted = fx->accept_counts ? h->d_accepted : nullptr;
+        hipError_t le = launch_pose_update(h->dof, kind, h->stream, b, sh, ma, m);
+        if (le == hipSuccess && fx->accept_counts)
+          le = launch_fix_count(h->stream, h->d_accepted, B, slot, fx->accept_counts);
+        return le;
+      };
+      if (kinds & UWVK_FIX_XY) HIPCHK(fix(MK_XY, 0, 2, fx->xy + (int64_t)fx->xy_index[e] * B * 2, fx->xy_cov, nullptr));
+      if (kinds & UWVK_FIX_Z) HIPCHK(fix(MK_Z, 1, 1, fx->z + (int64_t)fx->z_index[e] * B, &fx->z_cov, nullptr));
+      if (kinds & UWVK_FIX_GEO)
+        HIPCHK(fix(MK_GEO, 2, 2, fx->geo + (int64_t)fx->geo_index[e] * B * 2, fx->geo_cov, fx->gps_in_body));
     }
     return UWVK_OK;
   }
-  // PSP: the launches of plan_epochs (uwvk_plan.hpp), in order
-  const EpochPlan plan = plan_epochs(hf, first, count, facts(h));
+  // PSP: the launches of plan_fix_epochs (uwvk_plan.hpp; plan_epochs' without fixes), in order
+  const EpochPlan plan = plan_fix_epochs(hf, fx ? fx->host_flags + first : nullptr, first, count, facts(h));
   for (const Launch& l : plan.launches) {
     ea.first = l.first;
     ea.count = l.count;
+    if (l.kind == FIX) {
+      // the epoch's position fixes in one launch; they leave pdec as it is
+      const int64_t e = l.first;
+      FixArgs fa{};
+      fa.kinds = l.ev_any;
+      if (fa.kinds & UWVK_FIX_XY) fa.xy = fx->xy + (int64_t)fx->xy_index[e] * B * 2;
+      if (fa.kinds & UWVK_FIX_Z) fa.z = fx->z + (int64_t)fx->z_index[e] * B;
+      if (fa.kinds & UWVK_FIX_GEO) fa.geo = fx->geo + (int64_t)fx->geo_index[e] * B * 2;
+      std::memcpy(fa.xy_cov, fx->xy_cov, sizeof(fa.xy_cov));
+      fa.z_cov = fx->z_cov;
+      std::memcpy(fa.geo_cov, fx->geo_cov, sizeof(fa.geo_cov));
+      std::memcpy(fa.gps_in_body, fx->gps_in_body, sizeof(fa.gps_in_body));
+      fa.accept_counts = fx->accept_counts;
+      HIPCHK(launch_psp_fix(h->dof, h->stream, b, sh, fa));
+      continue;
+    }
     if (l.kind == EFFORTS) {
       // constrainVelocity (PEffVO) or the full measurementEfforts (psp_update_eff)
       if (!l.vo) h->pdec = false;  // the full model couples the parameters (PD off from here)
@@ -684,12 +722,38 @@ int64_t uwvk_pose_track_records(int64_t first, int64_t count, int64_t every) {
 // uwvk_pose_run_log_track (the range cut after every record epoch,
 // track_segments; after a segment that ends in one, the snapshot of the state
 // its last launch stored, and the statistics, into record r's slots)
+// uwvk_pose_run_log_fixes' argument check over epochs [first, first + count):
+// every flagged kind has its index and payload arrays and a row inside them
+// (an out-of-range row would be an out-of-bounds device read)
+static bool fixes_valid(const uwvk_pose_fixes* fx, int64_t first, int64_t count) {
+  if (!fx->host_flags) return false;
+  struct K {
+    uint32_t bit;
+    const int32_t* index;
+    const double* rows;
+    int64_t n;
+  } ks[3] = {{UWVK_FIX_XY, fx->xy_index, fx->xy, fx->n_xy},
+             {UWVK_FIX_Z, fx->z_index, fx->z, fx->n_z},
+             {UWVK_FIX_GEO, fx->geo_index, fx->geo, fx->n_geo}};
+  for (int64_t e = first; e < first + count; e++) {
+    const uint32_t f = fx->host_flags[e];
+    if (f & ~(UWVK_FIX_XY | UWVK_FIX_Z | UWVK_FIX_GEO)) return false;
+    for (const K& k : ks)
+      if ((f & k.bit) && (!k.index || !k.rows || k.index[e] < 0 || k.index[e] >= k.n)) return false;
+  }
+  return true;
+}
+
+// uwvk_pose_run_log_fixes: fx non-null adds the position fixes (a fix epoch ends
+// a launch, plan_fix_epochs; the track's snapshot of that epoch follows its FIX launch)
 static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
-                           uint32_t* accept_counts, const uwvk_pose_track* track) {
+                           uint32_t* accept_counts, const uwvk_pose_track* track,
+                           const uwvk_pose_fixes* fx = nullptr) {
   if (!h || !log || first < 0 || count < 0 || first + count > log->epochs || log->adcp_cells > 8) return UWVK_EINVAL;
   if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->stats) ||
                 track->capacity < track_records(first, count, track->every)))
     return UWVK_EINVAL;
+  if (fx && !fixes_valid(fx, first, count)) return UWVK_EINVAL;
   if (!h->has_state) return UWVK_ENOTINIT;
   // ABI 3: a hand-off timeout of an earlier, completed launch is reported here
   // (or by uwvk_pose_synchronize), before any new work is queued
@@ -728,11 +792,11 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
     ea.efforts_only = 0;
   }
   const PoseShared sh = h->sh;  // after upload_shared (it refreshes the Q shape)
-  if (!track) return run_epochs(h, b, sh, ea, hf, first, count);
+  if (!track) return run_epochs(h, b, sh, ea, hf, first, count, fx);
   const int s = h->store, nout = 3 * s + 2;
   int64_t r = 0;  // the next record of this call
   for (const TrackSegment& seg : track_segments(first, count, track->every)) {
-    const uwvk_status st = run_epochs(h, b, sh, ea, hf ? hf + (seg.first - first) : nullptr, seg.first, seg.count);
+    const uwvk_status st = run_epochs(h, b, sh, ea, hf ? hf + (seg.first - first) : nullptr, seg.first, seg.count, fx);
     if (st != UWVK_OK) return st;
     if (!seg.record) continue;
     if (track->mean || track->variance)
@@ -757,6 +821,13 @@ uwvk_status uwvk_pose_run_log_track(uwvk_pose* h, const uwvk_pose_log* log, int6
                                     uint32_t* accept_counts, const uwvk_pose_track* track) {
   UWVK_DEVICE_GUARD(h);
   return run_log(h, log, first, count, accept_counts, track);
+}
+
+uwvk_status uwvk_pose_run_log_fixes(uwvk_pose* h, const uwvk_pose_log* log, const uwvk_pose_fixes* fixes,
+                                    int64_t first, int64_t count, uint32_t* accept_counts,
+                                    const uwvk_pose_track* track) {
+  UWVK_DEVICE_GUARD(h);
+  return run_log(h, log, first, count, accept_counts, track, fixes);
 }
 
 uwvk_status uwvk_pose_ensemble_stats(uwvk_pose* h, const double* truth, double* out) {

@@ -73,6 +73,18 @@ struct EpochArgs {
   uint32_t units;       // tail0 + chunks * r_x
 };
 
+// one fix epoch of uwvk_pose_run_log_fixes (k_psp_fix): the host has resolved
+// the epoch's row indices, the kernel reads no index on the device
+struct FixArgs {
+  uint32_t kinds;           // UWVK_FIX_* present at this epoch
+  const double* xy;         // [batch][2], the epoch's row (valid when UWVK_FIX_XY)
+  const double* z;          // [batch]
+  const double* geo;        // [batch][2] lat, lon (rad)
+  double xy_cov[4], z_cov, geo_cov[4];
+  double gps_in_body[3];
+  uint32_t* accept_counts;  // [batch][3] XY, Z, GEO accepted (nullable)
+};
+
 // host-callable launchers (grid = one workgroup per instance)
 hipError_t launch_pose_predict(int dof, hipStream_t st, const PoseBufs& b, const PoseShared& sh, double dt);
 hipError_t launch_pose_update(int dof, int kind, hipStream_t st, const PoseBufs& b, const PoseShared& sh,

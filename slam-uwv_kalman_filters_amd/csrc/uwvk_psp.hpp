@@ -38,6 +38,13 @@ hipError_t launch_psp_update(int dof, int kind, hipStream_t st, const PoseBufs& 
 // (constrainVelocity, PEffVO), 0 the full measurementEfforts (psp_update_eff)
 hipError_t launch_psp_efforts(int dof, int vo, hipStream_t st, const PoseBufs& b, const PoseShared& sh,
                               const EpochArgs& ea);
+// run_log's fix epoch: the position fixes fa.kinds of one epoch, XY -> Z ->
+// Geographic, in one launch (k_psp_fix)
+template <int SR>
+hipError_t launch_psp_fix_sr(int dof, hipStream_t st, const PoseBufs& b, const PoseShared& sh, const FixArgs& fa);
+extern template hipError_t launch_psp_fix_sr<0>(int, hipStream_t, const PoseBufs&, const PoseShared&, const FixArgs&);
+extern template hipError_t launch_psp_fix_sr<1>(int, hipStream_t, const PoseBufs&, const PoseShared&, const FixArgs&);
+hipError_t launch_psp_fix(int dof, hipStream_t st, const PoseBufs& b, const PoseShared& sh, const FixArgs& fa);
 #include <vector>
 // grid 0: one block per instance; otherwise 8 (n_x + (chunks - 1) r_x)
 // ev_any: the OR of the launch's epoch flags (selects the kernel instantiation;

@@ -270,12 +270,45 @@ UWVK_DEV void copy_zr(const double* zin, const double* Rin, double (&z)[M], doub
   for (int k = 0; k < M * M; k++) R[k] = Rin[k];
 }
 
+// the position kinds (XY, Z, GEO, DELAYED: linear in the position rows, PXY /
+// PZ, k = 0 sigma points), shared by do_update and k_psp_fix.  v3: gps_in_body
+// (GEO); extra: delayed_xy [batch][2] (DELAYED)
+template <int DOF, int KIND, int SR, int NW = DOF>
+UWVK_DEV bool do_update_pos(PspSmem<DOF>& sm, const PoseShared& sh, int64_t inst, const double* zin,
+                            const double* Rin, const double* v3, const double* extra, bool* ok, double ds, double ids,
+                            Stamper* st = nullptr) {
+  using L = Lay<DOF>;
+  if constexpr (KIND == MK_XY || KIND == MK_GEO || KIND == MK_DELAYED) {
+    double z[2], R[4];
+    copy_zr<2>(zin, Rin, z, R);
+    int gate = 0;
+    if constexpr (KIND == MK_GEO) {  // PoseUKF.cpp:571-578
+      double r[3];
+      const double x = (zin[0] - sh.lat0) * sh.rm;
+      const double y = -(zin[1] - sh.lon0) * sh.rn_cos;
+      qrot(sm.mu + L::s_quat, v3, r);
+      z[0] = x - r[0];
+      z[1] = y - r[1];
+      gate = 1;
+    }
+    if constexpr (KIND == MK_DELAYED) {  // PoseUKF.cpp:516-521
+      z[0] = zin[0] + (sm.mu[L::s_pos] - extra[2 * inst]);
+      z[1] = zin[1] + (sm.mu[L::s_pos + 1] - extra[2 * inst + 1]);
+    }
+    return psp_update<DOF, SR, PXY<DOF>, NW>(sm, z, R, gate, PXY<DOF>{}, ok, ds, ids, st);
+  } else {
+    static_assert(KIND == MK_Z, "PSP update kind");
+    double z[1], R[1];
+    copy_zr<1>(zin, Rin, z, R);
+    return psp_update<DOF, SR, PZ<DOF>, NW>(sm, z, R, 0, PZ<DOF>{}, ok, ds, ids, st);
+  }
+}
+
 // one measurement update of kind KIND on instance inst (PSP form, SO3 side SR)
 // NW: the filter's n for the sigma-point weights (psp_update)
 template <int DOF, int KIND, int SR, int NW = DOF>
 UWVK_DEV bool do_update(PspSmem<DOF>& sm, const PoseShared& sh, int64_t inst, const double* zin, const double* Rin,
                         const MeasArgs& ma, bool* ok, double ds, double ids, Stamper* st = nullptr) {
-  using L = Lay<DOF>;
   if constexpr (KIND == MK_ACC) {
     double z[3], R[9];
     copy_zr<3>(zin, Rin, z, R);
@@ -297,29 +330,8 @@ UWVK_DEV bool do_update(PspSmem<DOF>& sm, const PoseShared& sh, int64_t inst, co
     PWater<DOF> h;
     h.cw = ma.extra ? ma.extra[inst] : 0.0;
     return psp_update<DOF, SR, PWater<DOF>, NW>(sm, z, R, 1, h, ok, ds, ids, st);
-  } else if constexpr (KIND == MK_XY || KIND == MK_GEO || KIND == MK_DELAYED) {
-    double z[2], R[4];
-    copy_zr<2>(zin, Rin, z, R);
-    int gate = 0;
-    if constexpr (KIND == MK_GEO) {  // PoseUKF.cpp:571-578
-      double r[3];
-      const double x = (zin[0] - sh.lat0) * sh.rm;
-      const double y = -(zin[1] - sh.lon0) * sh.rn_cos;
-      qrot(sm.mu + L::s_quat, ma.v3, r);
-      z[0] = x - r[0];
-      z[1] = y - r[1];
-      gate = 1;
-    }
-    if constexpr (KIND == MK_DELAYED) {  // PoseUKF.cpp:516-521
-      z[0] = zin[0] + (sm.mu[L::s_pos] - ma.extra[2 * inst]);
-      z[1] = zin[1] + (sm.mu[L::s_pos + 1] - ma.extra[2 * inst + 1]);
-    }
-    return psp_update<DOF, SR, PXY<DOF>, NW>(sm, z, R, gate, PXY<DOF>{}, ok, ds, ids, st);
   } else {
-    static_assert(KIND == MK_Z, "PSP update kind");
-    double z[1], R[1];
-    copy_zr<1>(zin, Rin, z, R);
-    return psp_update<DOF, SR, PZ<DOF>, NW>(sm, z, R, 0, PZ<DOF>{}, ok, ds, ids, st);
+    return do_update_pos<DOF, KIND, SR, NW>(sm, sh, inst, zin, Rin, ma.v3, ma.extra, ok, ds, ids, st);
   }
 }
 
@@ -829,6 +841,66 @@ __global__ __launch_bounds__(64) void k_psp_efforts(PoseBufs b, PoseShared sh, E
   store_psp<DOF>(sm, b, inst);
 }
 
+// run_log's fix epoch (uwvk_pose_run_log_fixes): after the launches of the
+// epoch's other updates, its position fixes XY -> Z -> Geographic in one Sigma
+// round trip, each through the single-call kernel's do_update_pos with
+// ds = ids = 1 (the result is k_psp_update's per kind, bitwise).  fa.kinds is
+// a kernel argument: the branches on it are wave-uniform.  A non-finite value
+// (or covariance) skips that kind for this instance (UWVK_ST_NAN), as
+// k_psp_update does; an instance with nothing to apply is not loaded or stored.
+template <int DOF, int SR>
+__global__ __launch_bounds__(64) void k_psp_fix(PoseBufs b, PoseShared sh, FixArgs fa) {
+  __shared__ PspSmem<DOF> sm;
+  const int64_t inst = xcd_instance(b.batch);
+  const double* zxy = fa.xy + inst * 2;
+  const double* zz = fa.z + inst;
+  const double* zg = fa.geo + inst * 2;
+  bool nan = false;
+  bool do_xy = false, do_z = false, do_geo = false;
+  if (fa.kinds & UWVK_FIX_XY) {
+    do_xy = all_finite(zxy, 2) && all_finite(fa.xy_cov, 4);
+    nan = nan || !do_xy;
+  }
+  if (fa.kinds & UWVK_FIX_Z) {
+    do_z = all_finite(zz, 1) && all_finite(&fa.z_cov, 1);
+    nan = nan || !do_z;
+  }
+  if (fa.kinds & UWVK_FIX_GEO) {
+    do_geo = all_finite(zg, 2) && all_finite(fa.geo_cov, 4);
+    nan = nan || !do_geo;
+  }
+  if (nan && lane_id() == 0) b.status[inst] |= UWVK_ST_NAN;
+  if (!(do_xy || do_z || do_geo)) return;
+  load_psp<DOF>(sm, b, inst);
+  bool sok = true;
+  bool axy = false, az = false, ageo = false;
+  if (do_xy) {
+    bool ok = true;
+    axy = do_update_pos<DOF, MK_XY, SR>(sm, sh, inst, zxy, fa.xy_cov, fa.gps_in_body, nullptr, &ok, 1.0, 1.0);
+    sok = sok && ok;
+  }
+  if (do_z) {
+    bool ok = true;
+    az = do_update_pos<DOF, MK_Z, SR>(sm, sh, inst, zz, &fa.z_cov, fa.gps_in_body, nullptr, &ok, 1.0, 1.0);
+    sok = sok && ok;
+  }
+  if (do_geo) {
+    bool ok = true;
+    ageo = do_update_pos<DOF, MK_GEO, SR>(sm, sh, inst, zg, fa.geo_cov, fa.gps_in_body, nullptr, &ok, 1.0, 1.0);
+    sok = sok && ok;
+  }
+  if (lane_id() == 0) {
+    if (!sok) b.status[inst] |= UWVK_ST_NOTPD;
+    if (fa.accept_counts) {
+      uint32_t* c = fa.accept_counts + inst * 3;
+      if (do_xy) c[0] += axy ? 1u : 0u;
+      if (do_z) c[1] += az ? 1u : 0u;
+      if (do_geo) c[2] += ageo ? 1u : 0u;
+    }
+  }
+  store_psp<DOF>(sm, b, inst);
+}
+
 }  // namespace psp
 
 template <int DOF, int SR>
@@ -881,6 +953,14 @@ hipError_t launch_psp_efforts_sr(int dof, int vo, hipStream_t st, const PoseBufs
   return hipGetLastError();
 }
 
+template <int SR>
+hipError_t launch_psp_fix_sr(int dof, hipStream_t st, const PoseBufs& b, const PoseShared& sh, const FixArgs& fa) {
+  const dim3 g((unsigned)b.batch), t(64);
+  if (dof == 53) hipLaunchKernelGGL((psp::k_psp_fix<53, SR>), g, t, 0, st, b, sh, fa);
+  else hipLaunchKernelGGL((psp::k_psp_fix<26, SR>), g, t, 0, st, b, sh, fa);
+  return hipGetLastError();
+}
+
 template <int DOF, int QM, int EVS, int SR, int PD = 0>
 static void launch_epoch_q(hipStream_t st, const PoseBufs& b, const PoseShared& sh, const EpochArgs& ea, dim3 g,
                            uint32_t pad) {
@@ -926,6 +1006,7 @@ template hipError_t launch_psp_epoch_sr<PSP_SIDE>(int, hipStream_t, const PoseBu
                                                   const EpochArgs&, int64_t, uint32_t, uint32_t, int);
 template hipError_t launch_psp_efforts_sr<PSP_SIDE>(int, int, hipStream_t, const PoseBufs&, const PoseShared&,
                                                     const EpochArgs&);
+template hipError_t launch_psp_fix_sr<PSP_SIDE>(int, hipStream_t, const PoseBufs&, const PoseShared&, const FixArgs&);
 
 #if PSP_SIDE == 0
 // the handle's side picks the instantiation set (a template parameter of every
@@ -949,6 +1030,10 @@ hipError_t launch_psp_epoch(int dof, hipStream_t st, const PoseBufs& b, const Po
 hipError_t launch_psp_efforts(int dof, int vo, hipStream_t st, const PoseBufs& b, const PoseShared& sh,
                               const EpochArgs& ea) {
   return sh.so3_right ? launch_psp_efforts_sr<1>(dof, vo, st, b, sh, ea) : launch_psp_efforts_sr<0>(dof, vo, st, b, sh, ea);
+}
+
+hipError_t launch_psp_fix(int dof, hipStream_t st, const PoseBufs& b, const PoseShared& sh, const FixArgs& fa) {
+  return sh.so3_right ? launch_psp_fix_sr<1>(dof, st, b, sh, fa) : launch_psp_fix_sr<0>(dof, st, b, sh, fa);
 }
 
 // XCC placement probe: block b writes the XCC it runs on (hardware XCC_ID).

@@ -13,7 +13,8 @@
 //  * a lower-rate sample stamped t is released at the first IMU epoch whose
 //    stamp is >= t - time_epsilon (the aligner releases it once the IMU stream
 //    has passed it) and integrated after that epoch's predict + acceleration
-//    update, in the fixed order DVL, pressure, ADCP cells, BodyEfforts;
+//    update, in the fixed order DVL, pressure, ADCP cells, BodyEfforts, then
+//    the position fixes (uwvk_schedule_fixes) XY, Z, Geographic;
 //  * two samples of one sensor landing in one epoch are queued: the later
 //    one moves to the next free epoch (order is kept, nothing is merged);
 //  * samples before the first IMU stamp or queued past the last epoch are
@@ -99,6 +100,36 @@ extern "C" uwvk_status uwvk_schedule_streams(const uwvk_stream_times* in, double
     out->dropped[k] = place(imu, E, ks[k].t, ks[k].n, time_epsilon, ks[k].bit, out->flags, ks[k].idx, extra,
                             UWVK_EV_EFFORTS_VELOCITY_ONLY);
     out->kept[k] = ks[k].n - out->dropped[k];
+  }
+  return UWVK_OK;
+}
+
+// The position fixes of a recording (uwvk_pose_fixes): XY, Z and GPS stamps
+// placed on the IMU epochs by the same place() as the other sensors, into
+// their own flags array (UWVK_FIX_*).
+extern "C" uwvk_status uwvk_schedule_fixes(const double* imu, int64_t n_imu, const double* xy_t, int64_t n_xy,
+                                           const double* z_t, int64_t n_z, const double* geo_t, int64_t n_geo,
+                                           double time_epsilon, uint32_t* flags, int32_t* xy_index, int32_t* z_index,
+                                           int32_t* geo_index, int64_t kept[3], int64_t dropped[3]) {
+  if (!imu || n_imu < 1 || !flags || !kept || !dropped || !(time_epsilon >= 0.0)) return UWVK_EINVAL;
+  if (!ascending(imu, n_imu)) return UWVK_EINVAL;
+  struct K {
+    const double* t;
+    int64_t n;
+    int32_t* idx;
+    uint32_t bit;
+  } ks[3] = {{xy_t, n_xy, xy_index, UWVK_FIX_XY}, {z_t, n_z, z_index, UWVK_FIX_Z}, {geo_t, n_geo, geo_index, UWVK_FIX_GEO}};
+  for (int k = 0; k < 3; k++) {
+    if (ks[k].n < 0 || (ks[k].n > 0 && (!ks[k].t || !ks[k].idx))) return UWVK_EINVAL;
+    if (!ascending(ks[k].t, ks[k].n)) return UWVK_EINVAL;
+  }
+  for (int64_t e = 0; e < n_imu; e++) flags[e] = 0;
+  for (int k = 0; k < 3; k++) {
+    kept[k] = 0;
+    dropped[k] = 0;
+    if (!ks[k].idx) continue;
+    dropped[k] = place(imu, n_imu, ks[k].t, ks[k].n, time_epsilon, ks[k].bit, flags, ks[k].idx, nullptr, 0);
+    kept[k] = ks[k].n - dropped[k];
   }
   return UWVK_OK;
 }

@@ -45,4 +45,19 @@ hipError_t launch_pose_track(int dof, hipStream_t st, const double* mu, const do
   return hipGetLastError();
 }
 
+// the literal path of uwvk_pose_run_log_fixes: k_pose_update's accepted bytes
+// of one fix kind added to the fix accept counts [batch][3]
+__global__ __launch_bounds__(kTrackThreads) void k_fix_count(const uint8_t* __restrict__ accepted, int64_t batch,
+                                                             int kind, uint32_t* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * kTrackThreads + threadIdx.x;
+  if (i < batch) counts[i * 3 + kind] += accepted[i] ? 1u : 0u;
+}
+
+hipError_t launch_fix_count(hipStream_t st, const uint8_t* accepted, int64_t batch, int kind, uint32_t* counts) {
+  if (!accepted || !counts || batch <= 0 || kind < 0 || kind > 2) return hipErrorInvalidValue;
+  const int64_t blocks = (batch + kTrackThreads - 1) / kTrackThreads;
+  hipLaunchKernelGGL(k_fix_count, dim3((unsigned)blocks), dim3(kTrackThreads), 0, st, accepted, batch, kind, counts);
+  return hipGetLastError();
+}
+
 }  // namespace uwvk

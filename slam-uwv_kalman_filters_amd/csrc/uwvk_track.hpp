@@ -11,4 +11,7 @@ namespace uwvk {
 hipError_t launch_pose_track(int dof, hipStream_t st, const double* mu, const double* sigma, int64_t batch,
                              double* mean, double* variance);
 
+// counts[i][kind] += accepted[i] != 0 (the literal path's fix accept counts, [batch][3])
+hipError_t launch_fix_count(hipStream_t st, const uint8_t* accepted, int64_t batch, int kind, uint32_t* counts);
+
 }  // namespace uwvk

@@ -581,6 +581,13 @@ class PoseUKF {
                    uint32_t* accept_counts = nullptr) {
     check(uwvk_pose_run_log_track(h_, &log, first, count, accept_counts, &track), "runLogTrack");
   }
+  // runLog with position fixes (uwvk_pose_run_log_fixes): the XY, Z and GPS
+  // fixes of `fixes` are applied at their epochs, after that epoch's other
+  // updates, one fused launch per fix epoch; track (nullable) as runLogTrack.
+  void runLogFixes(const uwvk_pose_log& log, const uwvk_pose_fixes& fixes, int64_t first, int64_t count,
+                   uint32_t* accept_counts = nullptr, const uwvk_pose_track* track = nullptr) {
+    check(uwvk_pose_run_log_fixes(h_, &log, &fixes, first, count, accept_counts, track), "runLogFixes");
+  }
   void synchronize() { check(uwvk_pose_synchronize(h_), "synchronize"); }
 
  private:

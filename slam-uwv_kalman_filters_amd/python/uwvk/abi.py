@@ -79,6 +79,13 @@ class PoseTrack(C.Structure):  # uwvk_pose_track (device buffers; truth is a hos
                 ("truth", P)]
 
 
+class PoseFixes(C.Structure):  # uwvk_pose_fixes (flags / indices host, payloads device)
+    _fields_ = [("host_flags", P), ("xy_index", P), ("xy", P), ("n_xy", C.c_int64), ("xy_cov", _arr(D, 4)),
+                ("z_index", P), ("z", P), ("n_z", C.c_int64), ("z_cov", D),
+                ("geo_index", P), ("geo", P), ("n_geo", C.c_int64), ("geo_cov", _arr(D, 4)),
+                ("gps_in_body", _arr(D, 3)), ("accept_counts", P)]
+
+
 class VelLog(C.Structure):  # uwvk_vel_log (device pointers)
     _fields_ = [("epochs", C.c_int64), ("dt", D), ("flags", P), ("gyro", P), ("efforts", P),
                 ("dvl_index", P), ("dvl", P), ("dvl_cov", _arr(D, 9)),
@@ -104,6 +111,10 @@ EV_PRESSURE = 0x4
 EV_ADCP = 0x8
 EV_EFFORTS = 0x10
 EV_EFFORTS_VELOCITY_ONLY = 0x20
+# position-fix flags (uwvk_pose_fixes.host_flags)
+FIX_XY = 0x1
+FIX_Z = 0x2
+FIX_GEO = 0x4
 
 STATUS = {0: "UWVK_OK", 1: "UWVK_EINVAL", 2: "UWVK_ENAN", 3: "UWVK_ENOTPD", 4: "UWVK_ENOMODEL",
           5: "UWVK_EDEVICE", 6: "UWVK_ENOMEM", 7: "UWVK_ENOTINIT", 8: "UWVK_ESCHEDULE"}

@@ -46,6 +46,7 @@ SYMBOLS = [
     "uwvk_pose_tail_chunks", "uwvk_pose_resident_slots", "uwvk_pose_epoch_qshape", "uwvk_pose_param_block", "uwvk_pose_pair_active", "uwvk_pose_timer_mark", "uwvk_pose_timer_elapsed",
     "uwvk_xcd_round_robin", "uwvk_synth_normal", "uwvk_synth_normal_at",
     "uwvk_pose_track_records", "uwvk_pose_run_log_track",
+    "uwvk_pose_run_log_fixes", "uwvk_schedule_fixes",
 ]
 
 _LIB = None
@@ -339,12 +340,20 @@ class PoseUKFBatch:
     def upload_log(self, log):
         return DevicePoseLog(log, self.device)
 
-    def run_log(self, dlog, first=0, count=None, accept_counts=None, sync=True):
+    def upload_fixes(self, fixes, counts=False):
+        return DevicePoseFixes(fixes, self.batch, self.device, counts)
+
+    def run_log(self, dlog, first=0, count=None, accept_counts=None, sync=True, fixes=None):
         """Queue epochs [first, first+count) on the handle's stream (PSP: one
-        launch per run of epochs without BodyEfforts); sync=False leaves them in flight."""
+        launch per run of epochs without BodyEfforts); sync=False leaves them in flight.
+        fixes: a DevicePoseFixes, the position fixes of the log (uwvk_pose_run_log_fixes)."""
         count = dlog.epochs - first if count is None else count
-        _chk(self.L.uwvk_pose_run_log(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count),
-                                      accept_counts.ptr if accept_counts is not None else None), "run_log")
+        ac = accept_counts.ptr if accept_counts is not None else None
+        if fixes is None:
+            _chk(self.L.uwvk_pose_run_log(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count), ac), "run_log")
+        else:
+            _chk(self.L.uwvk_pose_run_log_fixes(self.h, C.byref(dlog.s), C.byref(fixes.s), C.c_int64(first),
+                                                C.c_int64(count), ac, None), "run_log_fixes")
         if sync:
             self.synchronize()
 
@@ -353,14 +362,15 @@ class PoseUKFBatch:
         return int(self.L.uwvk_pose_track_records(first, count, every))
 
     def run_log_track(self, dlog, every, first=0, count=None, accept_counts=None, mean=True, variance=True,
-                      stats=False, truth=None, sync=True, capacity=None):
+                      stats=False, truth=None, sync=True, capacity=None, fixes=None):
         """run_log with a record of all instances after every absolute epoch e
         with (e + 1) % every == 0 (uwvk_pose_run_log_track): the means, the
         diagonal of Sigma and / or the ensemble statistics against truth
         ([records][store], host; None: ensemble_stats' None).  The records stay
         in device memory, written on the handle's stream; the returned PoseTrack
         reads them back.  capacity: records to allocate for (default: what the
-        range takes)."""
+        range takes).  fixes: a DevicePoseFixes (uwvk_pose_run_log_fixes); the
+        record of a fix epoch holds the state after its fixes."""
         count = dlog.epochs - first if count is None else count
         n = self.track_records(first, count, every)
         cap = n if capacity is None else int(capacity)
@@ -378,9 +388,13 @@ class PoseUKFBatch:
         tr.every, tr.capacity = int(every), cap
         tr.mean, tr.variance, tr.stats = (bufs[k].ptr if bufs[k] else None for k in ("mean", "variance", "stats"))
         tr.truth = _p(t)
-        _chk(self.L.uwvk_pose_run_log_track(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count),
-                                            accept_counts.ptr if accept_counts is not None else None,
-                                            C.byref(tr)), "run_log_track")
+        ac = accept_counts.ptr if accept_counts is not None else None
+        if fixes is None:
+            _chk(self.L.uwvk_pose_run_log_track(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count), ac,
+                                                C.byref(tr)), "run_log_track")
+        else:
+            _chk(self.L.uwvk_pose_run_log_fixes(self.h, C.byref(dlog.s), C.byref(fixes.s), C.c_int64(first),
+                                                C.c_int64(count), ac, C.byref(tr)), "run_log_fixes")
         if sync:
             self.synchronize()
         epochs = (np.arange(first // every + 1, first // every + 1 + n, dtype=np.int64) * every - 1)
@@ -484,6 +498,51 @@ class DevicePoseLog:
         s.host_flags = self.host_flags.ctypes.data
         self.s = s
         self.epochs = s.epochs
+
+
+class DevicePoseFixes:
+    """uwvk_pose_fixes: the position fixes of a log.  The payloads go to device
+    memory; the flags and index arrays stay on the host (kept alive here).
+    fixes: {"flags" [epochs] FIX_*, and per kind k in xy / z / geo (optional):
+    k + "_index" [epochs], k [n][batch][2] ([n][batch] for z), k + "_cov",
+    "gps_in_body"}.  counts: allocate the [batch][3] accept counts (zeroed)."""
+
+    KINDS = (("xy", 2), ("z", 1), ("geo", 2))
+
+    def __init__(self, fixes, batch, device=0, counts=False):
+        self.bufs, self.host = {}, {}
+        s = abi.PoseFixes()
+        self.host["flags"] = np.ascontiguousarray(fixes["flags"], dtype=np.uint32)
+        s.host_flags = self.host["flags"].ctypes.data
+        self.epochs = len(self.host["flags"])
+        for k, m in self.KINDS:
+            if fixes.get(k) is None:
+                continue
+            shape = (-1, batch, 2) if m == 2 else (-1, batch)
+            rows = np.ascontiguousarray(fixes[k], dtype=np.float64).reshape(shape)
+            self.host[k + "_index"] = np.ascontiguousarray(fixes[k + "_index"], dtype=np.int32)
+            if len(self.host[k + "_index"]) != self.epochs:
+                raise ValueError("%s_index: %d entries, the flags have %d" % (k, len(self.host[k + "_index"]), self.epochs))
+            self.bufs[k] = DeviceBuffer(rows, device)
+            setattr(s, k + "_index", self.host[k + "_index"].ctypes.data)
+            setattr(s, k, self.bufs[k].ptr)
+            setattr(s, "n_" + k, rows.shape[0])
+            cov = np.asarray(fixes[k + "_cov"], dtype=np.float64).ravel()
+            if m == 2:
+                abi.fill(getattr(s, k + "_cov"), cov)
+            else:
+                s.z_cov = float(cov[0])
+        abi.fill(s.gps_in_body, fixes.get("gps_in_body", (0.0, 0.0, 0.0)))
+        self.batch = batch
+        if counts:
+            self.bufs["counts"] = DeviceBuffer(np.zeros((batch, 3), np.uint32), device)
+            s.accept_counts = self.bufs["counts"].ptr
+        self.s = s
+
+    def accept_counts(self, stream=None):
+        """[batch][3] XY, Z, GEO accepted so far (None without counts)."""
+        b = self.bufs.get("counts")
+        return None if b is None else b.read(np.uint32, (self.batch, 3), stream)
 
 
 class VelocityUKFBatch:

@@ -10,6 +10,9 @@ pressure / ADCP / BodyEfforts integrated as their samples arrive
 each lower-rate sample to its epoch; `build_pose_log()` assembles the log dict
 that PoseUKFBatch.upload_log / the oracle's run_log consume.  `save()` /
 `load()` keep a mission in one .npz file (plain arrays, no pickles).
+Position fixes (XY, Z, GPS: PoseUKF.cpp:498-512, 567-579) are scheduled the same
+way by `schedule_fixes()` (uwvk_schedule_fixes) and travel in the log's "fixes"
+dict (PoseUKFBatch.upload_fixes, uwvk_pose_run_log_fixes).
 
 Payload arrays are per instance ([samples][batch][m]) or broadcast to the batch
 ([samples][m]); ADCP pings carry all cells: [pings][cells][batch][2].
@@ -59,6 +62,29 @@ def schedule(imu_t, dvl_t=None, pressure_t=None, adcp_t=None, efforts_t=None, ef
     return out
 
 
+FIXES = ("xy", "z", "geo")
+
+
+def schedule_fixes(imu_t, xy_t=None, z_t=None, geo_t=None, time_epsilon=1e-9):
+    """uwvk_schedule_fixes: the position-fix stamps placed on the IMU epochs by
+    the rule of schedule().  Returns dict(flags [E] FIX_*, xy_index, z_index,
+    geo_index, kept [3], dropped [3])."""
+    imu_t = np.ascontiguousarray(imu_t, np.float64)
+    E = len(imu_t)
+    ts = [np.zeros(0) if t is None else np.ascontiguousarray(t, np.float64) for t in (xy_t, z_t, geo_t)]
+    out = dict(flags=np.zeros(E, np.uint32))
+    for k in FIXES:
+        out[k + "_index"] = np.full(E, -1, np.int32)
+    kept, dropped = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+    args = [_p(imu_t), C.c_int64(E)]
+    for t in ts:
+        args += [_p(t) if len(t) else None, C.c_int64(len(t))]
+    args += [C.c_double(time_epsilon), _p(out["flags"])] + [_p(out[k + "_index"]) for k in FIXES] + [kept, dropped]
+    _chk(lib().uwvk_schedule_fixes(*args), "uwvk_schedule_fixes")
+    out.update(kept=np.array(kept[:]), dropped=np.array(dropped[:]))
+    return out
+
+
 def cell_weighting(water_velocity, cells, correlation=None):
     """uwvk_adcp_cell_weighting: per-cell weight of the lower water layer and validity."""
     w = np.zeros(cells)
@@ -81,8 +107,12 @@ def _per_instance(a, batch, tail):
 
 def build_pose_log(batch, imu_t, gyro, acc, acc_cov, dvl=None, pressure=None, adcp=None, efforts=None,
                    pressure_sensor_in_imu=(0.0, 0.0, 0.0), adcp_cell_weighting=None, dt_tolerance=0.05,
-                   time_epsilon=1e-9):
+                   time_epsilon=1e-9, xy=None, z=None, geo=None, gps_in_body=(0.0, 0.0, 0.0)):
     """Log dict of a recorded mission.
+
+    xy / z / geo: position fixes, (stamps, mu, cov) like the other sensors (mu
+    [n][batch][2] or [n][2]; z [n][batch] or [n]; geo lat, lon in rad).  With any
+    of them the log carries a "fixes" dict (PoseUKFBatch.upload_fixes).
 
     gyro, acc: [E][batch][3] or [E][3].  dvl / pressure / efforts: (stamps, mu, cov)
     tuples, mu [n][batch][m] or [n][m].  adcp: (stamps, mu [n][cells][batch][2] or
@@ -142,6 +172,22 @@ def build_pose_log(batch, imu_t, gyro, acc, acc_cov, dvl=None, pressure=None, ad
         log.update(adcp=np.ascontiguousarray(mu), adcp_cells=cells, adcp_cell_weighting=w,
                    adcp_cov=np.asarray(adcp[2]))
     # efforts velocity-only flags are part of `flags` (UWVK_EV_EFFORTS_VELOCITY_ONLY)
+    given = dict(xy=xy, z=z, geo=geo)
+    if any(s is not None for s in given.values()):
+        fsch = schedule_fixes(imu_t, stamps(xy), stamps(z), stamps(geo), time_epsilon)
+        fx = dict(flags=fsch["flags"], kept=fsch["kept"], dropped=fsch["dropped"],
+                  gps_in_body=np.asarray(gps_in_body, np.float64))
+        for i, k in enumerate(FIXES):
+            s = given[k]
+            if s is None:
+                continue
+            t = np.asarray(s[0], np.float64)
+            lead = int(np.searchsorted(t, np.asarray(imu_t, np.float64)[0] - time_epsilon, side="left"))
+            mu = np.asarray(s[1], np.float64)[lead:lead + int(fsch["kept"][i])]
+            fx[k] = _per_instance(mu, batch, () if k == "z" else (2,))
+            fx[k + "_index"] = fsch[k + "_index"]
+            fx[k + "_cov"] = np.asarray(s[2], np.float64).reshape((1,) if k == "z" else (2, 2))
+        log["fixes"] = fx
     return log
 
 
@@ -152,7 +198,8 @@ def replay(filt, log, every, truth=None):
     truth ([records][store], one row per record epoch) adds the ensemble
     statistics against it.  Returns dict(epochs, mean [records][batch][store],
     variance [records][batch][dof], stats [records][3*store+2] or None)."""
-    track = filt.run_log_track(filt.upload_log(log), every, stats=truth is not None, truth=truth)
+    fixes = filt.upload_fixes(log["fixes"]) if log.get("fixes") is not None else None
+    track = filt.run_log_track(filt.upload_log(log), every, stats=truth is not None, truth=truth, fixes=fixes)
     return dict(epochs=track.epochs, mean=track.mean(), variance=track.variance(), stats=track.stats())
 
 
@@ -166,6 +213,8 @@ def save(path, log):
     """Write a (scheduled) pose log to one .npz (arrays only)."""
     d = {k: np.asarray(log[k]) for k in _ARRAYS}
     d.update({k: np.asarray(log[k]) for k in _SCALARS})
+    if log.get("fixes") is not None:  # the position fixes, as fixes_<name> arrays
+        d.update({"fixes_" + k: np.asarray(v) for k, v in log["fixes"].items()})
     np.savez(path, **d)
 
 
@@ -174,5 +223,8 @@ def load(path):
     with np.load(path, allow_pickle=False) as z:
         log = {k: z[k] for k in _ARRAYS}
         log.update({k: z[k].item() for k in _SCALARS})
+        fx = {k[len("fixes_"):]: z[k] for k in z.files if k.startswith("fixes_")}
+    if fx:
+        log["fixes"] = fx
     log["mode"] = "mission"
     return log
