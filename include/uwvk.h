@@ -53,7 +53,8 @@ extern "C" {
  *      UWVK_OPT_PERSIST defaults to 1 (no dispatch-order assumption);
  *      added within 3, purely additive (no existing struct, flag or entry
  *      point changed): uwvk_pose_fixes, UWVK_FIX_*, uwvk_pose_run_log_fixes,
- *      uwvk_schedule_fixes. */
+ *      uwvk_schedule_fixes; uwvk_pose_delayed, uwvk_pose_run_log_delayed,
+ *      uwvk_schedule_delayed. */
 #define UWVK_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
@@ -472,6 +473,57 @@ uwvk_status uwvk_pose_run_log_fixes(uwvk_pose* h, const uwvk_pose_log* log, cons
                                     int64_t first, int64_t count, uint32_t* accept_counts,
                                     const uwvk_pose_track* track /* nullable */);
 
+/* Delayed XY fixes (USBL / LBL: a fix stamped t reaches the vehicle seconds
+ * later; integrateDelayedPositionMeasurement, PoseUKF.cpp:514-527) as events of
+ * a device-resident run.  A delayed sample is a payload row r with two epochs:
+ *   latch epoch L[r] = latch_epoch[r]: after ALL updates of that epoch (its
+ *     fixes and any delayed update of another row included), every instance's
+ *     own position mu[pos.x, pos.y] is copied into latched[r];
+ *   arrival epoch A[r] (index[A[r]] == r), A[r] > L[r]: the delayed update runs
+ *     with delayed_xy = latched[r], z = xy[r] + (mu.xy - latched[r]).
+ * Order within an epoch: predict, Acceleration, DVL, pressure, ADCP cells,
+ * BodyEfforts, XY, Z, Geographic, delayed XY, the latches of that epoch, then a
+ * track record.  The reference leaves the lookup of the delayed position to its
+ * caller; this latch rule is the engine's own (unpinned), as the ADCP cell
+ * weighting is.  latch_epoch[r] == -1: the caller filled latched[r] itself and
+ * the run never writes that row (the reference's literal call form).
+ * `latched` belongs to the caller and survives calls: a row latched in one call
+ * may arrive in a later call over the adjacent range, and calls over adjacent
+ * ranges give, bitwise, what one call over the whole range gives. */
+typedef struct uwvk_pose_delayed {
+  const int32_t* index;        /* HOST [log->epochs]: row arriving at epoch e, or -1 */
+  const int32_t* latch_epoch;  /* HOST [n]: L[r], or -1 = caller-filled row */
+  const double*  xy;           /* DEVICE [n][batch][2] the measured positions */
+  int64_t n;
+  double xy_cov[4];            /* host, shared */
+  double* latched;             /* DEVICE [n][batch][2], written by the run at L[r], read at A[r] */
+  uint32_t* accept_counts;     /* DEVICE [batch], nullable, caller zeroes */
+} uwvk_pose_delayed;
+
+/* uwvk_pose_run_log_fixes (fixes may be NULL) with delayed XY rows: over
+ * [first, first + count) the call latches every row with L[r] in the range and
+ * applies every row arriving in the range.  delayed == NULL is
+ * uwvk_pose_run_log_fixes.  The result is bitwise that of uwvk_pose_run_log cut
+ * after every latch, fix and arrival epoch, with at each cut the single calls
+ * XY, Z, Geographic, then uwvk_pose_update_delayed_xy whose delayed_xy is the
+ * x[:, 0:2] uwvk_pose_get_state returned at that row's latch cut, then the
+ * latches: the final state, every track record, both accept-count arrays,
+ * delayed->accept_counts, the per-instance status, `latched`, and the kernel
+ * choice of later calls (a delayed update is linear in the position rows and
+ * leaves the parameter block decoupled).  A sample whose value, shared
+ * covariance or latched position is non-finite is skipped for that instance
+ * only (UWVK_ST_NAN, PoseUKF.cpp:523); the call does not fail.
+ * UWVK_EINVAL, with nothing queued and the state untouched, checked before the
+ * first launch: index, latch_epoch, xy or latched NULL while n > 0; n < 0; an
+ * index[e] outside [-1, n) at an epoch of the range; a latch_epoch[r] below -1
+ * or at or beyond log->epochs; a row arriving in the range with latch_epoch[r]
+ * >= its arrival epoch.  Otherwise the errors of uwvk_pose_run_log_fixes. */
+uwvk_status uwvk_pose_run_log_delayed(uwvk_pose* h, const uwvk_pose_log* log,
+                                      const uwvk_pose_fixes* fixes /* nullable */,
+                                      const uwvk_pose_delayed* delayed /* nullable */,
+                                      int64_t first, int64_t count, uint32_t* accept_counts,
+                                      const uwvk_pose_track* track /* nullable */);
+
 /* Ensemble statistics over the batch (for Monte-Carlo runs):
  * out[0..store)        = sum_i x_i (orientation quaternion summed componentwise)
  * out[store..2*store)  = sum_i x_i^2
@@ -672,6 +724,22 @@ uwvk_status uwvk_schedule_fixes(const double* imu, int64_t n_imu,
                                 const double* geo_t, int64_t n_geo, double time_epsilon,
                                 uint32_t* flags, int32_t* xy_index, int32_t* z_index, int32_t* geo_index,
                                 int64_t kept[3], int64_t dropped[3]);
+
+/* The delayed XY samples of a recording placed on its IMU epochs, for
+ * uwvk_pose_delayed: sample s is stamped stamp_t[s] and reaches the vehicle at
+ * arrival_t[s] >= stamp_t[s] (both arrays ascending, else UWVK_EINVAL).  By the
+ * rule of uwvk_schedule_streams the latch epoch L is the first epoch whose IMU
+ * stamp is >= stamp - time_epsilon, and the arrival epoch A is the largest of
+ * the first epoch with stamp >= arrival - time_epsilon, L + 1 (the update needs
+ * a latched position of an earlier epoch) and the next free arrival epoch (two
+ * arrivals in one epoch are queued).  A sample stamped before the first IMU
+ * stamp, or whose A falls past the last epoch, is dropped and counted; the kept
+ * samples are the payload rows, in order.  index [n_imu] receives the row
+ * arriving at each epoch (-1 = none), latch_epoch the L of the kept rows
+ * (capacity n). */
+uwvk_status uwvk_schedule_delayed(const double* imu, int64_t n_imu, const double* stamp_t,
+                                  const double* arrival_t, int64_t n, double time_epsilon,
+                                  int32_t* index, int32_t* latch_epoch, int64_t* kept, int64_t* dropped);
 
 /* ADCP cell weighting for integrateMeasurement(WaterVelocityMeasurement,
  * cell_weighting) (PoseUKF.cpp:133-151,604-611) from cell_size and

@@ -2,8 +2,8 @@
 // integers and host arrays (plain C++17, no HIP): which epoch kernel a handle
 // runs, how a log range splits into launches, the grid and tail layout of one
 // launch, and the process-noise tables.  uwvk_pose.hip does the copies and the
-// launches; tests/cpp/plan_test.cpp, track_plan_test.cpp and fix_plan_test.cpp
-// check this file on the CPU.
+// launches; tests/cpp/plan_test.cpp, track_plan_test.cpp, fix_plan_test.cpp and
+// delayed_plan_test.cpp check this file on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -150,10 +150,10 @@ inline bool runs_pair(const EpochFacts& f) {
   return f.dof == 26 ? f.q_simple : runs_pd(f);
 }
 
-enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EFFORTS, FIX };
+enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EFFORTS, FIX, LATCH };
 struct Launch {
   LaunchKind kind;
-  int64_t first, count;  // absolute epochs [first, first + count); EFFORTS, FIX: the one epoch
+  int64_t first, count;  // absolute epochs [first, first + count); EFFORTS, FIX, LATCH: the one epoch
   int pd;                // EPOCH_*: the parameter-decoupled form
   int vo;                // EFFORTS: the velocity-only form (UWVK_EV_EFFORTS_VELOCITY_ONLY)
   uint32_t ev_any;       // the OR of the epochs' flags (the kernel instantiation)
@@ -269,6 +269,46 @@ inline EpochPlan plan_fix_epochs(const uint32_t* host_flags, const uint32_t* fix
     p.launches.insert(p.launches.end(), piece.launches.begin(), piece.launches.end());
     f.pdec = p.pdec = piece.pdec;
     if (fix) p.launches.push_back({FIX, stop - 1, 1, 0, 0, fix_flags[stop - 1 - first]});
+    e = stop;
+  }
+  return p;
+}
+
+// Delayed XY (uwvk_pose_run_log_delayed).  delayed_flags: per epoch of the range
+// (or null: none) two internal bits, built by run_log from uwvk_pose_delayed's
+// index and latch_epoch arrays; they lie outside UWVK_FIX_*, so a FIX launch's
+// mask can hold the fix kinds and the arrival bit.
+constexpr uint32_t kDelayedArrive = 0x8u;  // a delayed row arrives at this epoch (its update runs)
+constexpr uint32_t kDelayedLatch = 0x10u;  // rows latch the position after this epoch's updates
+// A piece ends after any epoch with a fix flag, an arrival or a latch; each
+// piece is planned by plan_epochs on its own, pdec carried over, as in
+// plan_fix_epochs.  After the piece (and its EFFORTS launch if the epoch has
+// one): one FIX launch if the epoch has fixes or an arrival (ev_any the fix
+// kinds plus kDelayedArrive: the delayed update is the last of the epoch's
+// position updates, in the same launch), then one LATCH launch (ev_any
+// kDelayedLatch) if rows latch there, so a latch sees all updates of its epoch.
+// A delayed update is linear in the position rows like the other fixes: pd /
+// pair go on.  With null or all-zero delayed_flags the plan is plan_fix_epochs'.
+inline EpochPlan plan_delayed_epochs(const uint32_t* host_flags, const uint32_t* fix_flags,
+                                     const uint32_t* delayed_flags, int64_t first, int64_t count, EpochFacts f) {
+  EpochPlan p;
+  p.pdec = f.pdec;
+  const int64_t end = first + count;
+  auto fixes = [&](int64_t k) { return fix_flags ? fix_flags[k - first] : 0u; };
+  auto delayed = [&](int64_t k) { return delayed_flags ? delayed_flags[k - first] & (kDelayedArrive | kDelayedLatch) : 0u; };
+  for (int64_t e = first; e < end;) {
+    int64_t stop = e;
+    while (stop < end && !(fixes(stop) || delayed(stop))) stop++;
+    const bool event = stop < end;
+    if (event) stop++;  // the piece includes its event epoch
+    const EpochPlan piece = plan_epochs(host_flags + (e - first), e, stop - e, f);
+    p.launches.insert(p.launches.end(), piece.launches.begin(), piece.launches.end());
+    f.pdec = p.pdec = piece.pdec;
+    if (event) {
+      const uint32_t fix = fixes(stop - 1) | (delayed(stop - 1) & kDelayedArrive);
+      if (fix) p.launches.push_back({FIX, stop - 1, 1, 0, 0, fix});
+      if (delayed(stop - 1) & kDelayedLatch) p.launches.push_back({LATCH, stop - 1, 1, 0, 0, kDelayedLatch});
+    }
     e = stop;
   }
   return p;

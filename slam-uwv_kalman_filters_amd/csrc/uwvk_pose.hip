@@ -17,6 +17,7 @@ hipError_t launch_pose_visual(int dof, int right, hipStream_t st, const PoseBufs
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 using namespace uwvk;
@@ -607,8 +608,34 @@ static double* stats_partials(const uwvk_pose* h) { return h->d_scratch + 256 + 
 // after upload_shared.
 // fx: the position fixes of uwvk_pose_run_log_fixes (validated over the call's
 // range by fixes_valid), or null.
+// dl: the delayed XY rows of uwvk_pose_run_log_delayed over the call's range
+// (delayed_plan), or null.
+struct DelayedRun {
+  const uwvk_pose_delayed* d;
+  int64_t first;                                     // flags[k] is epoch first + k
+  std::vector<uint32_t> flags;                       // kDelayedArrive / kDelayedLatch per epoch of the call
+  std::vector<std::pair<int64_t, int32_t>> latches;  // (latch epoch, row) of the call's range, ascending
+};
+static_assert(kFixDelayed == kDelayedArrive, "FixArgs::kinds holds the planner's arrival bit");
+
+// the latches of epoch e: the state's XY position into every row with L[r] = e
+static hipError_t latch_epoch_rows(uwvk_pose* h, const DelayedRun& dl, int64_t e) {
+  auto it = std::lower_bound(dl.latches.begin(), dl.latches.end(), std::make_pair(e, (int32_t)-1));
+  LatchRows rows{};
+  hipError_t le = hipSuccess;
+  for (; le == hipSuccess && it != dl.latches.end() && it->first == e; ++it) {
+    rows.row[rows.n++] = it->second;
+    if (rows.n == kLatchRows) {
+      le = launch_pose_latch(h->dof, h->stream, h->d_mu, h->batch, dl.d->latched, rows);
+      rows.n = 0;
+    }
+  }
+  if (le == hipSuccess && rows.n > 0) le = launch_pose_latch(h->dof, h->stream, h->d_mu, h->batch, dl.d->latched, rows);
+  return le;
+}
+
 static uwvk_status run_epochs(uwvk_pose* h, const PoseBufs& b, const PoseShared& sh, EpochArgs ea, const uint32_t* hf,
-                              int64_t first, int64_t count, const uwvk_pose_fixes* fx) {
+                              int64_t first, int64_t count, const uwvk_pose_fixes* fx, const DelayedRun* dl) {
   const int64_t B = h->batch;
   if (use_dense(h)) {  // literal kernels: one fused launch per epoch
     for (int64_t e = first; e < first + count; e++) {
@@ -616,7 +643,8 @@ static uwvk_status run_epochs(uwvk_pose* h, const PoseBufs& b, const PoseShared&
       ea.count = 1;
       HIPCHK(launch_pose_epoch(h->dof, h->stream, b, sh, ea));
       const uint32_t kinds = fx ? fx->host_flags[e] : 0u;
-      if (!kinds) continue;
+      const uint32_t dk = dl ? dl->flags[(size_t)(e - dl->first)] : 0u;
+      if (!kinds && !dk) continue;
       // the epoch's fixes: the literal k_pose_update per kind, on the log's device rows
       auto fix = [&](int kind, int slot, int m, const double* row, const double* cov, const double* v3) {
         MeasArgs ma{};
@@ -634,27 +662,58 @@ static uwvk_status run_epochs(uwvk_pose* h, const PoseBufs& b, const PoseShared&
       if (kinds & UWVK_FIX_Z) HIPCHK(fix(MK_Z, 1, 1, fx->z + (int64_t)fx->z_index[e] * B, &fx->z_cov, nullptr));
       if (kinds & UWVK_FIX_GEO)
         HIPCHK(fix(MK_GEO, 2, 2, fx->geo + (int64_t)fx->geo_index[e] * B * 2, fx->geo_cov, fx->gps_in_body));
+      if (dk & kDelayedArrive) {
+        // the arriving delayed row: k_pose_update on its device rows, delayed_xy the latched row
+        const uwvk_pose_delayed* d = dl->d;
+        const int64_t off = (int64_t)d->index[e] * B * 2;
+        MeasArgs ma{};
+        ma.mu = d->xy + off;
+        std::memcpy(ma.shared_cov, d->xy_cov, sizeof(d->xy_cov));
+        ma.extra = d->latched + off;
+        ma.check_extra = 1;
+        ma.accepted = d->accept_counts ? h->d_accepted : nullptr;
+        HIPCHK(launch_pose_update(h->dof, MK_DELAYED, h->stream, b, sh, ma, 2));
+        if (d->accept_counts) HIPCHK(launch_delayed_count(h->stream, h->d_accepted, B, d->accept_counts));
+      }
+      if (dk & kDelayedLatch) HIPCHK(latch_epoch_rows(h, *dl, e));
     }
     return UWVK_OK;
   }
-  // PSP: the launches of plan_fix_epochs (uwvk_plan.hpp; plan_epochs' without fixes), in order
-  const EpochPlan plan = plan_fix_epochs(hf, fx ? fx->host_flags + first : nullptr, first, count, facts(h));
+  // PSP: the launches of plan_delayed_epochs (uwvk_plan.hpp; plan_fix_epochs' without delayed rows,
+  // plan_epochs' without fixes either), in order
+  const EpochPlan plan = plan_delayed_epochs(hf, fx ? fx->host_flags + first : nullptr,
+                                             dl ? dl->flags.data() + (first - dl->first) : nullptr, first, count,
+                                             facts(h));
   for (const Launch& l : plan.launches) {
     ea.first = l.first;
     ea.count = l.count;
+    if (l.kind == LATCH) {
+      HIPCHK(latch_epoch_rows(h, *dl, l.first));
+      continue;
+    }
     if (l.kind == FIX) {
-      // the epoch's position fixes in one launch; they leave pdec as it is
+      // the epoch's position fixes (and its arriving delayed row) in one launch; they leave pdec as it is
       const int64_t e = l.first;
       FixArgs fa{};
       fa.kinds = l.ev_any;
-      if (fa.kinds & UWVK_FIX_XY) fa.xy = fx->xy + (int64_t)fx->xy_index[e] * B * 2;
-      if (fa.kinds & UWVK_FIX_Z) fa.z = fx->z + (int64_t)fx->z_index[e] * B;
-      if (fa.kinds & UWVK_FIX_GEO) fa.geo = fx->geo + (int64_t)fx->geo_index[e] * B * 2;
-      std::memcpy(fa.xy_cov, fx->xy_cov, sizeof(fa.xy_cov));
-      fa.z_cov = fx->z_cov;
-      std::memcpy(fa.geo_cov, fx->geo_cov, sizeof(fa.geo_cov));
-      std::memcpy(fa.gps_in_body, fx->gps_in_body, sizeof(fa.gps_in_body));
-      fa.accept_counts = fx->accept_counts;
+      if (fa.kinds & kFixDelayed) {
+        const uwvk_pose_delayed* d = dl->d;
+        const int64_t off = (int64_t)d->index[e] * B * 2;
+        fa.dxy = d->xy + off;
+        fa.latched = d->latched + off;
+        std::memcpy(fa.dxy_cov, d->xy_cov, sizeof(fa.dxy_cov));
+        fa.delayed_counts = d->accept_counts;
+      }
+      if (fa.kinds & (UWVK_FIX_XY | UWVK_FIX_Z | UWVK_FIX_GEO)) {  // (an arrival alone: fx may be null)
+        if (fa.kinds & UWVK_FIX_XY) fa.xy = fx->xy + (int64_t)fx->xy_index[e] * B * 2;
+        if (fa.kinds & UWVK_FIX_Z) fa.z = fx->z + (int64_t)fx->z_index[e] * B;
+        if (fa.kinds & UWVK_FIX_GEO) fa.geo = fx->geo + (int64_t)fx->geo_index[e] * B * 2;
+        std::memcpy(fa.xy_cov, fx->xy_cov, sizeof(fa.xy_cov));
+        fa.z_cov = fx->z_cov;
+        std::memcpy(fa.geo_cov, fx->geo_cov, sizeof(fa.geo_cov));
+        std::memcpy(fa.gps_in_body, fx->gps_in_body, sizeof(fa.gps_in_body));
+        fa.accept_counts = fx->accept_counts;
+      }
       HIPCHK(launch_psp_fix(h->dof, h->stream, b, sh, fa));
       continue;
     }
@@ -746,14 +805,48 @@ static bool fixes_valid(const uwvk_pose_fixes* fx, int64_t first, int64_t count)
 
 // uwvk_pose_run_log_fixes: fx non-null adds the position fixes (a fix epoch ends
 // a launch, plan_fix_epochs; the track's snapshot of that epoch follows its FIX launch)
+// uwvk_pose_run_log_delayed's argument check, and the per-epoch delayed flags
+// and latch list of [first, first + count) (out).  An out-of-range row would be
+// an out-of-bounds device access.
+static bool delayed_plan(const uwvk_pose_delayed* d, int64_t epochs, int64_t first, int64_t count, DelayedRun* out) {
+  if (d->n < 0) return false;
+  if (d->n > 0 && (!d->index || !d->latch_epoch || !d->xy || !d->latched)) return false;
+  out->d = d;
+  out->first = first;
+  out->flags.assign((size_t)count, 0u);
+  for (int64_t r = 0; r < d->n; r++) {
+    const int64_t L = d->latch_epoch[r];
+    if (L < -1 || L >= epochs) return false;
+    if (L >= first && L < first + count) {
+      out->flags[(size_t)(L - first)] |= kDelayedLatch;
+      out->latches.emplace_back(L, (int32_t)r);
+    }
+  }
+  std::sort(out->latches.begin(), out->latches.end());
+  if (!d->index) return true;  // n == 0, no index array: no events
+  for (int64_t e = first; e < first + count; e++) {
+    const int64_t r = d->index[e];
+    if (r < -1 || r >= d->n) return false;
+    if (r < 0) continue;
+    if (d->latch_epoch[r] >= e) return false;
+    out->flags[(size_t)(e - first)] |= kDelayedArrive;
+  }
+  return true;
+}
+
+// uwvk_pose_run_log_delayed: dly non-null adds the delayed XY rows (an arrival
+// and a latch end a launch, plan_delayed_epochs)
 static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
                            uint32_t* accept_counts, const uwvk_pose_track* track,
-                           const uwvk_pose_fixes* fx = nullptr) {
+                           const uwvk_pose_fixes* fx = nullptr, const uwvk_pose_delayed* dly = nullptr) {
   if (!h || !log || first < 0 || count < 0 || first + count > log->epochs || log->adcp_cells > 8) return UWVK_EINVAL;
   if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->stats) ||
                 track->capacity < track_records(first, count, track->every)))
     return UWVK_EINVAL;
   if (fx && !fixes_valid(fx, first, count)) return UWVK_EINVAL;
+  DelayedRun drun{};
+  if (dly && !delayed_plan(dly, log->epochs, first, count, &drun)) return UWVK_EINVAL;
+  const DelayedRun* dl = dly ? &drun : nullptr;
   if (!h->has_state) return UWVK_ENOTINIT;
   // ABI 3: a hand-off timeout of an earlier, completed launch is reported here
   // (or by uwvk_pose_synchronize), before any new work is queued
@@ -792,11 +885,11 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
     ea.efforts_only = 0;
   }
   const PoseShared sh = h->sh;  // after upload_shared (it refreshes the Q shape)
-  if (!track) return run_epochs(h, b, sh, ea, hf, first, count, fx);
+  if (!track) return run_epochs(h, b, sh, ea, hf, first, count, fx, dl);
   const int s = h->store, nout = 3 * s + 2;
   int64_t r = 0;  // the next record of this call
   for (const TrackSegment& seg : track_segments(first, count, track->every)) {
-    const uwvk_status st = run_epochs(h, b, sh, ea, hf ? hf + (seg.first - first) : nullptr, seg.first, seg.count, fx);
+    const uwvk_status st = run_epochs(h, b, sh, ea, hf ? hf + (seg.first - first) : nullptr, seg.first, seg.count, fx, dl);
     if (st != UWVK_OK) return st;
     if (!seg.record) continue;
     if (track->mean || track->variance)
@@ -828,6 +921,13 @@ uwvk_status uwvk_pose_run_log_fixes(uwvk_pose* h, const uwvk_pose_log* log, cons
                                     const uwvk_pose_track* track) {
   UWVK_DEVICE_GUARD(h);
   return run_log(h, log, first, count, accept_counts, track, fixes);
+}
+
+uwvk_status uwvk_pose_run_log_delayed(uwvk_pose* h, const uwvk_pose_log* log, const uwvk_pose_fixes* fixes,
+                                      const uwvk_pose_delayed* delayed, int64_t first, int64_t count,
+                                      uint32_t* accept_counts, const uwvk_pose_track* track) {
+  UWVK_DEVICE_GUARD(h);
+  return run_log(h, log, first, count, accept_counts, track, fixes, delayed);
 }
 
 uwvk_status uwvk_pose_ensemble_stats(uwvk_pose* h, const double* truth, double* out) {

@@ -18,6 +18,7 @@ struct MeasArgs {
   const double* extra; // cell_weighting [batch] / delayed_xy [batch][2]
   double v3[3];        // sensor_in_imu / gps_in_body
   int only_vel;
+  int check_extra;     // MK_DELAYED in a run (uwvk_pose_run_log_delayed): a non-finite delayed_xy skips the instance
 };
 
 struct EpochArgs {
@@ -73,16 +74,25 @@ struct EpochArgs {
   uint32_t units;       // tail0 + chunks * r_x
 };
 
+// kinds bit of a delayed XY row arriving at this epoch (uwvk_pose_run_log_delayed;
+// the planner's kDelayedArrive, outside UWVK_FIX_*)
+constexpr uint32_t kFixDelayed = 0x8u;
 // one fix epoch of uwvk_pose_run_log_fixes (k_psp_fix): the host has resolved
 // the epoch's row indices, the kernel reads no index on the device
 struct FixArgs {
-  uint32_t kinds;           // UWVK_FIX_* present at this epoch
+  uint32_t kinds;           // UWVK_FIX_* present at this epoch, and kFixDelayed
   const double* xy;         // [batch][2], the epoch's row (valid when UWVK_FIX_XY)
   const double* z;          // [batch]
   const double* geo;        // [batch][2] lat, lon (rad)
   double xy_cov[4], z_cov, geo_cov[4];
   double gps_in_body[3];
   uint32_t* accept_counts;  // [batch][3] XY, Z, GEO accepted (nullable)
+  // kFixDelayed: the arriving row's measured positions, the positions latched
+  // at its stamp's epoch (delayed_xy), the shared covariance, the accept counts
+  const double* dxy;         // [batch][2]
+  const double* latched;     // [batch][2]
+  double dxy_cov[4];
+  uint32_t* delayed_counts;  // [batch] (nullable)
 };
 
 // host-callable launchers (grid = one workgroup per instance)
@@ -287,7 +297,10 @@ __global__ __launch_bounds__(Geo<DOF>::T) UWVK_UPD_ATTR void k_pose_update(PoseB
   }
   const double* z = ma.mu + i * m;
   const double* R = ma.cov ? ma.cov + i * m * m : ma.shared_cov;
-  if (!all_finite(z, m) || !all_finite(R, m * m)) {  // checkMeasurment [EXT]
+  bool finite = all_finite(z, m) && all_finite(R, m * m);  // checkMeasurment [EXT]
+  if constexpr (K == MK_DELAYED)  // the shifted measurement's check (PoseUKF.cpp:523) for a latched row
+    if (ma.check_extra) finite = finite && all_finite(ma.extra + 2 * i, 2);
+  if (!finite) {
     if (tid() == 0) {
       b.status[i] |= UWVK_ST_NAN;
       if (ma.accepted) ma.accepted[i] = 0;

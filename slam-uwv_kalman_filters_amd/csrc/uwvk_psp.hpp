@@ -39,7 +39,7 @@ hipError_t launch_psp_update(int dof, int kind, hipStream_t st, const PoseBufs& 
 hipError_t launch_psp_efforts(int dof, int vo, hipStream_t st, const PoseBufs& b, const PoseShared& sh,
                               const EpochArgs& ea);
 // run_log's fix epoch: the position fixes fa.kinds of one epoch, XY -> Z ->
-// Geographic, in one launch (k_psp_fix)
+// Geographic -> an arriving delayed XY row (kFixDelayed), in one launch (k_psp_fix)
 template <int SR>
 hipError_t launch_psp_fix_sr(int dof, hipStream_t st, const PoseBufs& b, const PoseShared& sh, const FixArgs& fa);
 extern template hipError_t launch_psp_fix_sr<0>(int, hipStream_t, const PoseBufs&, const PoseShared&, const FixArgs&);

@@ -848,15 +848,24 @@ __global__ __launch_bounds__(64) void k_psp_efforts(PoseBufs b, PoseShared sh, E
 // a kernel argument: the branches on it are wave-uniform.  A non-finite value
 // (or covariance) skips that kind for this instance (UWVK_ST_NAN), as
 // k_psp_update does; an instance with nothing to apply is not loaded or stored.
+// kFixDelayed (uwvk_pose_run_log_delayed): a delayed XY row arrives at this
+// epoch; its update runs last, after Geographic, with delayed_xy the position
+// latched at the row's stamp (fa.latched).  The shifted measurement
+// z = value + (mu.xy - latched) is checked as PoseUKF.cpp:523 checks it: a
+// non-finite latched position skips the row like a non-finite value.
+// The 26-DOF layout is held at the 7 waves per SIMD (<= 72 VGPRs) of its
+// k_psp_update<XY / GEO> kernels: with the fourth branch the allocator took 75
+// (6 waves) unasked; no scratch either way (tests/test_fix_kernel_resources.py).
 template <int DOF, int SR>
-__global__ __launch_bounds__(64) void k_psp_fix(PoseBufs b, PoseShared sh, FixArgs fa) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DOF == 26 ? 7 : 1))) void k_psp_fix(PoseBufs b, PoseShared sh, FixArgs fa) {
   __shared__ PspSmem<DOF> sm;
   const int64_t inst = xcd_instance(b.batch);
   const double* zxy = fa.xy + inst * 2;
   const double* zz = fa.z + inst;
   const double* zg = fa.geo + inst * 2;
+  const double* zd = fa.dxy + inst * 2;
   bool nan = false;
-  bool do_xy = false, do_z = false, do_geo = false;
+  bool do_xy = false, do_z = false, do_geo = false, do_dly = false;
   if (fa.kinds & UWVK_FIX_XY) {
     do_xy = all_finite(zxy, 2) && all_finite(fa.xy_cov, 4);
     nan = nan || !do_xy;
@@ -869,11 +878,15 @@ __global__ __launch_bounds__(64) void k_psp_fix(PoseBufs b, PoseShared sh, FixAr
     do_geo = all_finite(zg, 2) && all_finite(fa.geo_cov, 4);
     nan = nan || !do_geo;
   }
+  if (fa.kinds & kFixDelayed) {
+    do_dly = all_finite(zd, 2) && all_finite(fa.dxy_cov, 4) && all_finite(fa.latched + inst * 2, 2);
+    nan = nan || !do_dly;
+  }
   if (nan && lane_id() == 0) b.status[inst] |= UWVK_ST_NAN;
-  if (!(do_xy || do_z || do_geo)) return;
+  if (!(do_xy || do_z || do_geo || do_dly)) return;
   load_psp<DOF>(sm, b, inst);
   bool sok = true;
-  bool axy = false, az = false, ageo = false;
+  bool axy = false, az = false, ageo = false, adly = false;
   if (do_xy) {
     bool ok = true;
     axy = do_update_pos<DOF, MK_XY, SR>(sm, sh, inst, zxy, fa.xy_cov, fa.gps_in_body, nullptr, &ok, 1.0, 1.0);
@@ -889,8 +902,14 @@ __global__ __launch_bounds__(64) void k_psp_fix(PoseBufs b, PoseShared sh, FixAr
     ageo = do_update_pos<DOF, MK_GEO, SR>(sm, sh, inst, zg, fa.geo_cov, fa.gps_in_body, nullptr, &ok, 1.0, 1.0);
     sok = sok && ok;
   }
+  if (do_dly) {
+    bool ok = true;
+    adly = do_update_pos<DOF, MK_DELAYED, SR>(sm, sh, inst, zd, fa.dxy_cov, fa.gps_in_body, fa.latched, &ok, 1.0, 1.0);
+    sok = sok && ok;
+  }
   if (lane_id() == 0) {
     if (!sok) b.status[inst] |= UWVK_ST_NOTPD;
+    if (fa.delayed_counts && do_dly) fa.delayed_counts[inst] += adly ? 1u : 0u;
     if (fa.accept_counts) {
       uint32_t* c = fa.accept_counts + inst * 3;
       if (do_xy) c[0] += axy ? 1u : 0u;

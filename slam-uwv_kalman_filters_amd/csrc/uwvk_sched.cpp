@@ -18,7 +18,11 @@
 //  * two samples of one sensor landing in one epoch are queued: the later
 //    one moves to the next free epoch (order is kept, nothing is merged);
 //  * samples before the first IMU stamp or queued past the last epoch are
-//    dropped and counted.
+//    dropped and counted;
+//  * a delayed XY sample (uwvk_schedule_delayed) has two stamps: the filter's
+//    position is latched at the epoch its measurement stamp is released at, and
+//    the update runs, after Geographic, at the epoch its arrival stamp is
+//    released at, at least one epoch later.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -131,6 +135,44 @@ extern "C" uwvk_status uwvk_schedule_fixes(const double* imu, int64_t n_imu, con
     dropped[k] = place(imu, n_imu, ks[k].t, ks[k].n, time_epsilon, ks[k].bit, flags, ks[k].idx, nullptr, 0);
     kept[k] = ks[k].n - dropped[k];
   }
+  return UWVK_OK;
+}
+
+// Delayed XY samples (uwvk_pose_delayed): the stamp placed by the rule of
+// place() gives the latch epoch, the arrival placed the same way, but not before
+// L + 1 and queued behind the arrival before it, gives the arrival epoch.
+extern "C" uwvk_status uwvk_schedule_delayed(const double* imu, int64_t n_imu, const double* stamp_t,
+                                             const double* arrival_t, int64_t n, double time_epsilon, int32_t* index,
+                                             int32_t* latch_epoch, int64_t* kept, int64_t* dropped) {
+  if (!imu || n_imu < 1 || !index || !kept || !dropped || !(time_epsilon >= 0.0) || n < 0) return UWVK_EINVAL;
+  if (n > 0 && (!stamp_t || !arrival_t || !latch_epoch)) return UWVK_EINVAL;
+  if (!ascending(imu, n_imu) || !ascending(stamp_t, n) || !ascending(arrival_t, n)) return UWVK_EINVAL;
+  for (int64_t s = 0; s < n; s++)
+    if (!(arrival_t[s] >= stamp_t[s])) return UWVK_EINVAL;  // (a NaN stamp too)
+  const int64_t E = n_imu;
+  const double eps = time_epsilon;
+  for (int64_t e = 0; e < E; e++) index[e] = -1;
+  int64_t lost = 0, el = 0, ea = 0, next_free = 0;
+  int32_t row = 0;
+  for (int64_t s = 0; s < n; s++) {
+    if (!(stamp_t[s] >= imu[0] - eps)) {  // stamped before the first epoch
+      lost++;
+      continue;
+    }
+    while (el < E && imu[el] < stamp_t[s] - eps) el++;
+    while (ea < E && imu[ea] < arrival_t[s] - eps) ea++;
+    int64_t at = ea > el + 1 ? ea : el + 1;
+    if (next_free > at) at = next_free;
+    if (at >= E) {  // (el >= E lands here too)
+      lost++;
+      continue;
+    }
+    index[at] = row;
+    latch_epoch[row++] = (int32_t)el;
+    next_free = at + 1;
+  }
+  *kept = n - lost;
+  *dropped = lost;
   return UWVK_OK;
 }
 

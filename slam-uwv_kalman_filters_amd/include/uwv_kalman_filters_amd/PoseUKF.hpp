@@ -588,6 +588,14 @@ class PoseUKF {
                    uint32_t* accept_counts = nullptr, const uwvk_pose_track* track = nullptr) {
     check(uwvk_pose_run_log_fixes(h_, &log, &fixes, first, count, accept_counts, track), "runLogFixes");
   }
+  // runLogFixes (fixes nullable) with delayed XY rows (uwvk_pose_run_log_delayed):
+  // each row's own position is latched on the device after its latch epoch and
+  // the delayed update runs at its arrival epoch, after that epoch's fixes.
+  void runLogDelayed(const uwvk_pose_log& log, const uwvk_pose_fixes* fixes, const uwvk_pose_delayed& delayed,
+                     int64_t first, int64_t count, uint32_t* accept_counts = nullptr,
+                     const uwvk_pose_track* track = nullptr) {
+    check(uwvk_pose_run_log_delayed(h_, &log, fixes, &delayed, first, count, accept_counts, track), "runLogDelayed");
+  }
   void synchronize() { check(uwvk_pose_synchronize(h_), "synchronize"); }
 
  private:

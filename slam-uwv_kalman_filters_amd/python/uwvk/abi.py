@@ -86,6 +86,11 @@ class PoseFixes(C.Structure):  # uwvk_pose_fixes (flags / indices host, payloads
                 ("gps_in_body", _arr(D, 3)), ("accept_counts", P)]
 
 
+class PoseDelayed(C.Structure):  # uwvk_pose_delayed (index arrays host, payload and latched device)
+    _fields_ = [("index", P), ("latch_epoch", P), ("xy", P), ("n", C.c_int64), ("xy_cov", _arr(D, 4)),
+                ("latched", P), ("accept_counts", P)]
+
+
 class VelLog(C.Structure):  # uwvk_vel_log (device pointers)
     _fields_ = [("epochs", C.c_int64), ("dt", D), ("flags", P), ("gyro", P), ("efforts", P),
                 ("dvl_index", P), ("dvl", P), ("dvl_cov", _arr(D, 9)),

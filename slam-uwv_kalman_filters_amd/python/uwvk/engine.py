@@ -47,6 +47,7 @@ SYMBOLS = [
     "uwvk_xcd_round_robin", "uwvk_synth_normal", "uwvk_synth_normal_at",
     "uwvk_pose_track_records", "uwvk_pose_run_log_track",
     "uwvk_pose_run_log_fixes", "uwvk_schedule_fixes",
+    "uwvk_pose_run_log_delayed", "uwvk_schedule_delayed",
 ]
 
 _LIB = None
@@ -343,13 +344,21 @@ class PoseUKFBatch:
     def upload_fixes(self, fixes, counts=False):
         return DevicePoseFixes(fixes, self.batch, self.device, counts)
 
-    def run_log(self, dlog, first=0, count=None, accept_counts=None, sync=True, fixes=None):
+    def upload_delayed(self, delayed, counts=False):
+        return DevicePoseDelayed(delayed, self.batch, self.device, counts)
+
+    def run_log(self, dlog, first=0, count=None, accept_counts=None, sync=True, fixes=None, delayed=None):
         """Queue epochs [first, first+count) on the handle's stream (PSP: one
         launch per run of epochs without BodyEfforts); sync=False leaves them in flight.
-        fixes: a DevicePoseFixes, the position fixes of the log (uwvk_pose_run_log_fixes)."""
+        fixes: a DevicePoseFixes, the position fixes of the log (uwvk_pose_run_log_fixes).
+        delayed: a DevicePoseDelayed, its delayed XY rows (uwvk_pose_run_log_delayed)."""
         count = dlog.epochs - first if count is None else count
         ac = accept_counts.ptr if accept_counts is not None else None
-        if fixes is None:
+        if delayed is not None:
+            _chk(self.L.uwvk_pose_run_log_delayed(self.h, C.byref(dlog.s), C.byref(fixes.s) if fixes is not None else None,
+                                                  C.byref(delayed.s), C.c_int64(first), C.c_int64(count), ac, None),
+                 "run_log_delayed")
+        elif fixes is None:
             _chk(self.L.uwvk_pose_run_log(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count), ac), "run_log")
         else:
             _chk(self.L.uwvk_pose_run_log_fixes(self.h, C.byref(dlog.s), C.byref(fixes.s), C.c_int64(first),
@@ -362,7 +371,7 @@ class PoseUKFBatch:
         return int(self.L.uwvk_pose_track_records(first, count, every))
 
     def run_log_track(self, dlog, every, first=0, count=None, accept_counts=None, mean=True, variance=True,
-                      stats=False, truth=None, sync=True, capacity=None, fixes=None):
+                      stats=False, truth=None, sync=True, capacity=None, fixes=None, delayed=None):
         """run_log with a record of all instances after every absolute epoch e
         with (e + 1) % every == 0 (uwvk_pose_run_log_track): the means, the
         diagonal of Sigma and / or the ensemble statistics against truth
@@ -370,7 +379,9 @@ class PoseUKFBatch:
         in device memory, written on the handle's stream; the returned PoseTrack
         reads them back.  capacity: records to allocate for (default: what the
         range takes).  fixes: a DevicePoseFixes (uwvk_pose_run_log_fixes); the
-        record of a fix epoch holds the state after its fixes."""
+        record of a fix epoch holds the state after its fixes.  delayed: a
+        DevicePoseDelayed (uwvk_pose_run_log_delayed); a record follows the
+        epoch's delayed update and latches."""
         count = dlog.epochs - first if count is None else count
         n = self.track_records(first, count, every)
         cap = n if capacity is None else int(capacity)
@@ -389,7 +400,11 @@ class PoseUKFBatch:
         tr.mean, tr.variance, tr.stats = (bufs[k].ptr if bufs[k] else None for k in ("mean", "variance", "stats"))
         tr.truth = _p(t)
         ac = accept_counts.ptr if accept_counts is not None else None
-        if fixes is None:
+        if delayed is not None:
+            _chk(self.L.uwvk_pose_run_log_delayed(self.h, C.byref(dlog.s), C.byref(fixes.s) if fixes is not None else None,
+                                                  C.byref(delayed.s), C.c_int64(first), C.c_int64(count), ac,
+                                                  C.byref(tr)), "run_log_delayed")
+        elif fixes is None:
             _chk(self.L.uwvk_pose_run_log_track(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count), ac,
                                                 C.byref(tr)), "run_log_track")
         else:
@@ -543,6 +558,49 @@ class DevicePoseFixes:
         """[batch][3] XY, Z, GEO accepted so far (None without counts)."""
         b = self.bufs.get("counts")
         return None if b is None else b.read(np.uint32, (self.batch, 3), stream)
+
+
+class DevicePoseDelayed:
+    """uwvk_pose_delayed: the delayed XY rows of a log.  The payload and the
+    latched positions live in device memory; the index arrays stay on the host
+    (kept alive here).  delayed: {"index" [epochs] the row arriving at each
+    epoch or -1, "latch_epoch" [n] (-1: a caller-filled row), "xy" [n][batch][2],
+    "xy_cov" 2x2, optional "latched" [n][batch][2] (the caller-filled rows;
+    default zeros)}.  counts: allocate the [batch] accept counts (zeroed).  One
+    object may serve calls over adjacent ranges: a row latched in one call
+    arrives in a later one."""
+
+    def __init__(self, delayed, batch, device=0, counts=False):
+        self.bufs, self.host = {}, {}
+        s = abi.PoseDelayed()
+        self.host["index"] = np.ascontiguousarray(delayed["index"], dtype=np.int32)
+        self.host["latch_epoch"] = np.ascontiguousarray(delayed["latch_epoch"], dtype=np.int32)
+        rows = np.ascontiguousarray(delayed["xy"], dtype=np.float64).reshape(-1, batch, 2)
+        self.epochs, self.n, self.batch = len(self.host["index"]), rows.shape[0], batch
+        if len(self.host["latch_epoch"]) != self.n:
+            raise ValueError("latch_epoch: %d entries, xy has %d rows" % (len(self.host["latch_epoch"]), self.n))
+        latched = delayed.get("latched")
+        latched = np.zeros_like(rows) if latched is None else \
+            np.ascontiguousarray(latched, dtype=np.float64).reshape(rows.shape)
+        self.bufs["xy"] = DeviceBuffer(rows, device)
+        self.bufs["latched"] = DeviceBuffer(latched, device)
+        s.index = self.host["index"].ctypes.data
+        s.latch_epoch = self.host["latch_epoch"].ctypes.data
+        s.xy, s.latched, s.n = self.bufs["xy"].ptr, self.bufs["latched"].ptr, self.n
+        abi.fill(s.xy_cov, np.asarray(delayed["xy_cov"], dtype=np.float64).ravel())
+        if counts:
+            self.bufs["counts"] = DeviceBuffer(np.zeros(batch, np.uint32), device)
+            s.accept_counts = self.bufs["counts"].ptr
+        self.s = s
+
+    def accept_counts(self, stream=None):
+        """[batch] delayed updates accepted so far (None without counts)."""
+        b = self.bufs.get("counts")
+        return None if b is None else b.read(np.uint32, (self.batch,), stream)
+
+    def latched(self, stream=None):
+        """[n][batch][2] the latched positions (rows not yet latched as uploaded)."""
+        return self.bufs["latched"].read(np.float64, (self.n, self.batch, 2), stream)
 
 
 class VelocityUKFBatch:

@@ -12,7 +12,10 @@ that PoseUKFBatch.upload_log / the oracle's run_log consume.  `save()` /
 `load()` keep a mission in one .npz file (plain arrays, no pickles).
 Position fixes (XY, Z, GPS: PoseUKF.cpp:498-512, 567-579) are scheduled the same
 way by `schedule_fixes()` (uwvk_schedule_fixes) and travel in the log's "fixes"
-dict (PoseUKFBatch.upload_fixes, uwvk_pose_run_log_fixes).
+dict (PoseUKFBatch.upload_fixes, uwvk_pose_run_log_fixes).  Delayed XY fixes
+(USBL / LBL samples stamped t that arrive later, PoseUKF.cpp:514-527) are placed
+by `schedule_delayed()` (uwvk_schedule_delayed) and travel in the log's
+"delayed" dict (PoseUKFBatch.upload_delayed, uwvk_pose_run_log_delayed).
 
 Payload arrays are per instance ([samples][batch][m]) or broadcast to the batch
 ([samples][m]); ADCP pings carry all cells: [pings][cells][batch][2].
@@ -85,6 +88,26 @@ def schedule_fixes(imu_t, xy_t=None, z_t=None, geo_t=None, time_epsilon=1e-9):
     return out
 
 
+def schedule_delayed(imu_t, stamp_t, arrival_t, time_epsilon=1e-9):
+    """uwvk_schedule_delayed: delayed XY samples (stamped stamp_t, reaching the
+    vehicle at arrival_t >= stamp_t) placed on the IMU epochs by the rule of
+    schedule(): the latch epoch from the stamp, the arrival epoch from the
+    arrival, at least one epoch later, two arrivals in one epoch queued.
+    Returns dict(index [E] the row arriving at each epoch or -1, latch_epoch
+    [kept], kept, dropped)."""
+    imu_t = np.ascontiguousarray(imu_t, np.float64)
+    st, at = (np.ascontiguousarray(t, np.float64).ravel() for t in (stamp_t, arrival_t))
+    if len(st) != len(at):
+        raise ValueError("%d stamps, %d arrivals" % (len(st), len(at)))
+    E, n = len(imu_t), len(st)
+    index, latch = np.full(E, -1, np.int32), np.full(max(n, 1), -1, np.int32)
+    kept, dropped = C.c_int64(0), C.c_int64(0)
+    _chk(lib().uwvk_schedule_delayed(_p(imu_t), C.c_int64(E), _p(st) if n else None, _p(at) if n else None,
+                                     C.c_int64(n), C.c_double(time_epsilon), _p(index), _p(latch),
+                                     C.byref(kept), C.byref(dropped)), "uwvk_schedule_delayed")
+    return dict(index=index, latch_epoch=latch[:kept.value].copy(), kept=int(kept.value), dropped=int(dropped.value))
+
+
 def cell_weighting(water_velocity, cells, correlation=None):
     """uwvk_adcp_cell_weighting: per-cell weight of the lower water layer and validity."""
     w = np.zeros(cells)
@@ -107,12 +130,15 @@ def _per_instance(a, batch, tail):
 
 def build_pose_log(batch, imu_t, gyro, acc, acc_cov, dvl=None, pressure=None, adcp=None, efforts=None,
                    pressure_sensor_in_imu=(0.0, 0.0, 0.0), adcp_cell_weighting=None, dt_tolerance=0.05,
-                   time_epsilon=1e-9, xy=None, z=None, geo=None, gps_in_body=(0.0, 0.0, 0.0)):
+                   time_epsilon=1e-9, xy=None, z=None, geo=None, gps_in_body=(0.0, 0.0, 0.0), delayed_xy=None):
     """Log dict of a recorded mission.
 
     xy / z / geo: position fixes, (stamps, mu, cov) like the other sensors (mu
     [n][batch][2] or [n][2]; z [n][batch] or [n]; geo lat, lon in rad).  With any
     of them the log carries a "fixes" dict (PoseUKFBatch.upload_fixes).
+    delayed_xy: (stamps, arrivals, mu, cov), XY fixes stamped `stamps` that reach
+    the vehicle at `arrivals`; the log then carries a "delayed" dict
+    (PoseUKFBatch.upload_delayed).
 
     gyro, acc: [E][batch][3] or [E][3].  dvl / pressure / efforts: (stamps, mu, cov)
     tuples, mu [n][batch][m] or [n][m].  adcp: (stamps, mu [n][cells][batch][2] or
@@ -188,6 +214,14 @@ def build_pose_log(batch, imu_t, gyro, acc, acc_cov, dvl=None, pressure=None, ad
             fx[k + "_index"] = fsch[k + "_index"]
             fx[k + "_cov"] = np.asarray(s[2], np.float64).reshape((1,) if k == "z" else (2, 2))
         log["fixes"] = fx
+    if delayed_xy is not None:
+        t = np.asarray(delayed_xy[0], np.float64)
+        dsch = schedule_delayed(imu_t, t, delayed_xy[1], time_epsilon)
+        lead = int(np.searchsorted(t, np.asarray(imu_t, np.float64)[0] - time_epsilon, side="left"))
+        mu = np.asarray(delayed_xy[2], np.float64)[lead:lead + dsch["kept"]]
+        log["delayed"] = dict(index=dsch["index"], latch_epoch=dsch["latch_epoch"], xy=_per_instance(mu, batch, (2,)),
+                              xy_cov=np.asarray(delayed_xy[3], np.float64).reshape(2, 2),
+                              kept=np.int64(dsch["kept"]), dropped=np.int64(dsch["dropped"]))
     return log
 
 
@@ -199,7 +233,9 @@ def replay(filt, log, every, truth=None):
     statistics against it.  Returns dict(epochs, mean [records][batch][store],
     variance [records][batch][dof], stats [records][3*store+2] or None)."""
     fixes = filt.upload_fixes(log["fixes"]) if log.get("fixes") is not None else None
-    track = filt.run_log_track(filt.upload_log(log), every, stats=truth is not None, truth=truth, fixes=fixes)
+    delayed = filt.upload_delayed(log["delayed"]) if log.get("delayed") is not None else None
+    track = filt.run_log_track(filt.upload_log(log), every, stats=truth is not None, truth=truth, fixes=fixes,
+                               delayed=delayed)
     return dict(epochs=track.epochs, mean=track.mean(), variance=track.variance(), stats=track.stats())
 
 
@@ -215,6 +251,8 @@ def save(path, log):
     d.update({k: np.asarray(log[k]) for k in _SCALARS})
     if log.get("fixes") is not None:  # the position fixes, as fixes_<name> arrays
         d.update({"fixes_" + k: np.asarray(v) for k, v in log["fixes"].items()})
+    if log.get("delayed") is not None:  # the delayed XY rows, as delayed_<name> arrays
+        d.update({"delayed_" + k: np.asarray(v) for k, v in log["delayed"].items()})
     np.savez(path, **d)
 
 
@@ -224,7 +262,10 @@ def load(path):
         log = {k: z[k] for k in _ARRAYS}
         log.update({k: z[k].item() for k in _SCALARS})
         fx = {k[len("fixes_"):]: z[k] for k in z.files if k.startswith("fixes_")}
+        dl = {k[len("delayed_"):]: z[k] for k in z.files if k.startswith("delayed_")}
     if fx:
         log["fixes"] = fx
+    if dl:
+        log["delayed"] = dl
     log["mode"] = "mission"
     return log
