@@ -834,7 +834,9 @@ uwvk_status uwvk_bottom_predict(uwvk_bottom* h, double dt);
 uwvk_status uwvk_bottom_update_range(uwvk_bottom* h, const double* mu, const double* cov, double shared_cov,
                                      const double unit_direction[3], const double origin[3], const uint8_t* mask);
 /* integrateMeasurement(NormalType, cov) (BottomUKF.cpp:63-67): mu batch*3 (normalised),
- * cov batch*4 (NULL = shared_cov[4]) */
+ * cov batch*4 (NULL = shared_cov[4]).  A non-finite mean or covariance of a
+ * masked-in instance fails the call with UWVK_ENAN, a zero-length mean with
+ * UWVK_EINVAL; both change nothing. */
 uwvk_status uwvk_bottom_update_normal(uwvk_bottom* h, const double* mu, const double* cov, const double* shared_cov,
                                       const uint8_t* mask);
 uwvk_status uwvk_bottom_get_state(uwvk_bottom* h, double* x, double* P);

@@ -11,6 +11,14 @@ strongest available guard against a restatement bug.
 Sources restated: PoseUKF.cpp:12-84 (process), :107-219 (measurements),
 :288-372 (init), :393-465 (noise / predict), :476-611 (update wiring, gates),
 :685-699; VelocityUKF.cpp:6-130; PoseState.hpp:29-45.
+
+Second part (the small filters, checked against oracle/uwvk_small_oracle.c):
+BottomUKF.cpp:5-67, IndirectPoseUKF.cpp:7-142, PoseUKF.cpp:221-244 and
+:613-654, DESIGN.md §3 items 1-4 and 11.  Written from those sources, not from
+the C file, and in a different form on purpose: S2 through the rotation matrix
+R_x = I + [v]x + [v]x^2 / (1 + x_z), v = e3 x x (the C and HIP code use two
+basis vectors), the visual model through composed rotation matrices (they use
+step-wise quaternion sandwiches).
 """
 import numpy as np
 
@@ -127,6 +135,95 @@ class VecLayout:
         return X - M
 
 
+# ---------------------------------------------------------------- S2
+def skew(v):
+    z = np.zeros_like(v[..., 0])
+    return np.stack([np.stack([z, -v[..., 2], v[..., 1]], -1), np.stack([v[..., 2], z, -v[..., 0]], -1),
+                     np.stack([-v[..., 1], v[..., 0], z], -1)], -2)
+
+
+def s2_rot(x):
+    """R_x, the minimal rotation taking e3 to x: I + [v]x + [v]x^2 / (1 + x_z), v = e3 x x."""
+    x = np.asarray(x, dtype=float)
+    K = skew(np.cross(np.array([0.0, 0.0, 1.0]), x))
+    return np.eye(3) + K + K @ K / (1.0 + x[..., 2])[..., None, None]
+
+
+def s2_from(v):
+    """MTK::S2(v): the normalised vector."""
+    v = np.asarray(v, dtype=float)
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def s2_plus(x, d):
+    """x [+] d = R_x (sinc|d| d, cos|d|)."""
+    d = np.asarray(d, dtype=float)
+    t = np.linalg.norm(d, axis=-1, keepdims=True)
+    sc = np.where(t > 0, np.sin(t) / np.where(t > 0, t, 1.0), 1.0)
+    e = np.concatenate([sc * d, np.cos(t)], -1)
+    return (s2_rot(x) @ e[..., None])[..., 0]
+
+
+def s2_minus(y, x):
+    """y [-] x = log(R_x^T y), log(w) = atan2(|w12|, w3) w12 / |w12|."""
+    w = (np.swapaxes(s2_rot(x), -1, -2) @ np.asarray(y, dtype=float)[..., None])[..., 0]
+    nn = np.linalg.norm(w[..., :2], axis=-1, keepdims=True)
+    k = np.where(nn > 0, np.arctan2(nn, w[..., 2:]) / np.where(nn > 0, nn, 1.0), 0.0)
+    return k * w[..., :2]
+
+
+class S2Layout:
+    """A single S2 value (the measurement manifold of the normal and bearing updates)."""
+    dof = 2
+
+    def boxplus(self, X, D):
+        return s2_plus(X, D)
+
+    def boxminus(self, X, M):
+        return s2_minus(X, M)
+
+
+class Compound:
+    """Compound manifold over segments ("v", dim) | ("so3",) | ("s2",), stored in
+    order: vect dim, quaternion (w, x, y, z), unit 3-vector.  `right` is the side
+    of every SO3 segment (MTK has one SO3::boxplus)."""
+
+    def __init__(self, segs, right=None):
+        self.right = SO3_RIGHT if right is None else right
+        self.segs = []
+        di = si = 0
+        for seg in segs:
+            kind = seg[0]
+            dd, ss = (seg[1], seg[1]) if kind == "v" else ((3, 4) if kind == "so3" else (2, 3))
+            self.segs.append((kind, slice(di, di + dd), slice(si, si + ss)))
+            di, si = di + dd, si + ss
+        self.dof, self.store = di, si
+
+    def boxplus(self, X, D):
+        X, D = np.asarray(X, dtype=float), np.asarray(D, dtype=float)
+        Y = np.empty(np.broadcast_shapes(X.shape[:-1], D.shape[:-1]) + (self.store,))
+        for kind, d, s in self.segs:
+            if kind == "v":
+                Y[..., s] = X[..., s] + D[..., d]
+            elif kind == "so3":
+                Y[..., s] = so3_plus(X[..., s], D[..., d], self.right)
+            else:
+                Y[..., s] = s2_plus(X[..., s], D[..., d])
+        return Y
+
+    def boxminus(self, X, M):
+        X, M = np.asarray(X, dtype=float), np.asarray(M, dtype=float)
+        D = np.empty(np.broadcast_shapes(X.shape[:-1], M.shape[:-1]) + (self.dof,))
+        for kind, d, s in self.segs:
+            if kind == "v":
+                D[..., d] = X[..., s] - M[..., s]
+            elif kind == "so3":
+                D[..., d] = so3_minus(X[..., s], M[..., s], self.right)
+            else:
+                D[..., d] = s2_minus(X[..., s], M[..., s])
+        return D
+
+
 # ---------------------------------------------------------------- UKF core
 def sigma_points(lay, mu, P):
     L = np.linalg.cholesky(P)
@@ -166,16 +263,24 @@ def ukf_predict(lay, mu, P, g, Qp):
 
 
 def ukf_update(lay, mu, P, z, h, R, zmanifold, gate):
+    """zmanifold: False (Eigen vector: plain average), True (vect manifold:
+    iterative mean) or a layout with boxplus / boxminus (a manifold-valued
+    measurement: iterative mean, deviations and innovation by [-])."""
     X = sigma_points(lay, mu, P)
     Z = h(X)
-    zm = vect_mean(Z) if zmanifold else Z.mean(axis=0)
-    dZ = Z - zm
+    if zmanifold is True or zmanifold is False:
+        zm = vect_mean(Z) if zmanifold else Z.mean(axis=0)
+        dZ = Z - zm
+        nu = z - zm
+    else:
+        zm = manifold_mean(zmanifold, Z)
+        dZ = zmanifold.boxminus(Z, zm)
+        nu = zmanifold.boxminus(z, zm)
     dX = lay.boxminus(X, mu)
     S = 0.5 * dZ.T @ dZ + R
     C = 0.5 * dX.T @ dZ
     Si = np.linalg.inv(S)
     K = C @ Si
-    nu = z - zm
     d2 = nu @ Si @ nu
     if gate and d2 > D2P95:
         return mu, P, False
@@ -509,6 +614,145 @@ class VelTwin:
     def update_pressure(self, z, R):
         self.mu, self.P, _ = ukf_update(self.lay, self.mu, self.P, np.atleast_1d(np.asarray(z, float)),
                                         lambda X: X[:, 3:4], np.atleast_2d(R), True, False)
+
+
+# ---------------------------------------------------------------- BottomUKF
+class BottomTwin:
+    """Single BottomUKF (BottomUKF.cpp): state {distance, normal (S2)}, stored (d, nx, ny, nz)."""
+
+    def __init__(self, x, P):
+        self.lay = Compound([("v", 1), ("s2",)])
+        x = np.array(x, float)
+        self.mu = np.concatenate([x[:1], s2_from(x[1:])])
+        self.P = np.array(P, float)
+        self.Q = np.eye(3)  # Covariance::Identity(), :45
+        self.velocity = np.zeros(3)
+
+    def predict(self, dt):
+        """predictionStepImpl :48-54, processModel :5-16."""
+        Qp = np.linalg.norm(self.velocity[:2]) ** 2.0 * dt ** 2.0 * self.Q
+        vinv = -1.0 * self.velocity[2]
+
+        def g(X):
+            Y = X.copy()
+            Y[:, 0] = X[:, 0] + vinv * dt
+            return Y
+        self.mu, self.P = ukf_predict(self.lay, self.mu, self.P, g, Qp)
+
+    def update_range(self, z, cov, direction, origin):
+        """integrateMeasurement(RangeMeasurement, ...) :56-61, measurementDistance :18-30."""
+        u, o = np.asarray(direction, float), np.asarray(origin, float)
+
+        def h(X):
+            n = X[:, 1:4]
+            bottom = np.stack([np.zeros(len(X)), np.zeros(len(X)), -X[:, 0]], -1)
+            v = n @ u
+            w = np.sum((bottom - o) * n, -1)
+            return np.where(v != 0.0, w / np.where(v != 0.0, v, 1.0), 0.0)[:, None]
+        self.mu, self.P, _ = ukf_update(self.lay, self.mu, self.P, np.atleast_1d(np.asarray(z, float)), h,
+                                        np.atleast_2d(np.asarray(cov, float)), True, False)
+
+    def update_normal(self, z, cov):
+        """integrateMeasurement(NormalType, cov) :63-67: an S2-valued measurement."""
+        self.mu, self.P, _ = ukf_update(self.lay, self.mu, self.P, s2_from(z), lambda X: X[:, 1:4],
+                                        np.asarray(cov, float), S2Layout(), False)
+
+
+# ---------------------------------------------------------------- visual landmark
+def qmats(Q):
+    """Rotation matrices [N, 3, 3] of quaternions [N, 4]."""
+    return np.moveaxis(qmat(np.asarray(Q).T), -1, 0)
+
+
+def visual_updates(lay, amu, asig, sm, body_pose, features, feature_cov, feature_pos, cam, cam_in):
+    """The feature loop of IndirectPoseUKF.cpp:109-131 / PoseUKF.cpp:628-649 on the
+    augmented state (marker position at storage offset sm, its quaternion after):
+    one S2-valued update per feature, accept_any_mahalanobis_distance.
+    body_pose(X) -> (R [N, 3, 3], t [N, 3]) of the body / IMU in nav per sigma point."""
+    fx2, fy2, fxy = cam[0] ** 2.0, cam[1] ** 2.0, cam[0] * cam[1]
+    Rc, tc = qmat(cam_in[3:7]), np.asarray(cam_in[:3], float)
+    for mu_px, cv, f in zip(np.asarray(features, float), np.asarray(feature_cov, float),
+                            np.asarray(feature_pos, float)):
+        z = s2_from(np.array([(mu_px[0] - cam[2]) / cam[0], (mu_px[1] - cam[3]) / cam[1], 1.0]))
+        R = np.array([[cv[0, 0] / fx2, cv[0, 1] / fxy], [cv[1, 0] / fxy, cv[1, 1] / fy2]])
+
+        def h(X):
+            Rb, tb = body_pose(X)
+            Rcn = Rb @ Rc                       # camera in nav: body_in_nav * cam_in_body
+            tcn = tb + Rb @ tc
+            fn = qmats(X[:, sm + 3:sm + 7]) @ f + X[:, sm:sm + 3]
+            fc = (np.swapaxes(Rcn, -1, -2) @ (fn - tcn)[..., None])[..., 0]  # its inverse
+            return s2_from(fc)
+        amu, asig, _ = ukf_update(lay, amu, asig, z, h, R, S2Layout(), False)
+    return amu, asig
+
+
+def _augment(mu, P, marker_pose, cov_marker):
+    n = P.shape[0]
+    amu = np.concatenate([mu, np.asarray(marker_pose, float)])
+    asig = np.zeros((n + 6, n + 6))
+    asig[:n, :n] = P
+    asig[n:, n:] = cov_marker
+    return amu, asig
+
+
+def _pose_update_visual(self, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in_imu):
+    """PoseUKF::integrateMeasurement(vector<VisualFeatureMeasurement>, ...), PoseUKF.cpp:613-654,
+    on PoseStateWithMarker (:225-228, n = dof + 6) with measurementVisualLandmark (:233-243)."""
+    n, s = self.lay.dof, self.lay.store
+    lay = Compound([("v", 3), ("so3",), ("v", n - 6), ("v", 3), ("so3",)], self.lay.right)
+    amu, asig = _augment(self.mu, self.P, marker_pose, cov_marker)
+    amu, asig = visual_updates(lay, amu, asig, s, lambda X: (qmats(X[:, 3:7]), X[:, 0:3]), features, feature_cov,
+                               feature_pos, cam, cam_in_imu)
+    self.mu, self.P = amu[:s], asig[:n, :n]
+
+
+PoseTwin.update_visual = _pose_update_visual
+
+
+# ---------------------------------------------------------------- IndirectPoseUKF
+class IndirectPoseTwin:
+    """Single IndirectPoseUKF (IndirectPoseUKF.cpp): state {position_error,
+    orientation_error (SO3)}, stored t(3) q(4); poses are t(3) q(4)."""
+
+    def __init__(self, pos_std, ori_std, tau, init_pos_err=None, init_pos_std=None):
+        self.lay = Compound([("v", 3), ("so3",)])
+        self.mu = np.concatenate([np.zeros(3) if init_pos_err is None else np.asarray(init_pos_err, float),
+                                  [1.0, 0.0, 0.0, 0.0]])
+        ips = np.ones(3) if init_pos_std is None else np.asarray(init_pos_std, float)
+        self.P = np.diag(np.concatenate([np.abs(ips) ** 2, np.abs(ori_std) ** 2]))
+        self.Q = np.diag(np.concatenate([np.abs(pos_std) ** 2, np.abs(ori_std) ** 2]))
+        self.tau = tau
+        self.ref = np.array([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0])
+
+    def predict(self, dt):
+        """predictionStepImpl :80-92, processModel :7-20."""
+        rot = qmat(self.mu[3:7])
+        Qp = self.Q.copy()
+        Qp[3:, 3:] = rot @ ((2.0 / (self.tau * dt)) * self.Q[3:, 3:]) @ rot.T
+        Qp = dt ** 2.0 * Qp
+
+        def g(X):
+            Y = X.copy()
+            d = (-1.0 / self.tau) * so3_log(X[:, 3:7])
+            Y[:, 3:7] = so3_plus(X[:, 3:7], d * dt, self.lay.right)
+            return Y
+        self.mu, self.P = ukf_predict(self.lay, self.mu, self.P, g, Qp)
+
+    def update_visual(self, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in_body):
+        """integrateMeasurement(marker_features, ...) :94-135 on FilterStateWithMarker (:26-30)."""
+        lay = Compound([("v", 3), ("so3",), ("v", 3), ("so3",)], self.lay.right)
+        amu, asig = _augment(self.mu, self.P, marker_pose, cov_marker)
+        Rr, tr = qmat(self.ref[3:7]), self.ref[:3]
+
+        def body(X):  # body_in_nav * pose_error, :42-45
+            return Rr @ qmats(X[:, 3:7]), tr + X[:, 0:3] @ Rr.T
+        amu, asig = visual_updates(lay, amu, asig, 7, body, features, feature_cov, feature_pos, cam, cam_in_body)
+        self.mu, self.P = amu[:7], asig[:6, :6]
+
+    def corrected_pose(self):
+        """getCorrectedPose :137-142: pose_ref * pose_error."""
+        return np.concatenate([self.ref[:3] + qmat(self.ref[3:7]) @ self.mu[:3], qmul(self.ref[3:7], self.mu[3:7])])
 
 
 def cfg_dict(c):

@@ -356,22 +356,26 @@ def _per(a, batch, tail):
     return np.ascontiguousarray(a)
 
 
-def _pose_visual(L, fn, ptr, batch, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in):
+def _pose_visual(L, fn, ptr, batch, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in,
+                 mask=None):
     f = _f64(features)
     nf = f.shape[1]
     fc = _per(feature_cov, batch, (nf, 2, 2))
     mp = _per(marker_pose, batch, (7,))
     fp, cm, cc, ci = _f64(feature_pos), _f64(cov_marker), _f64(cam), _f64(cam_in)
     for i in range(batch):
+        if mask is not None and not mask[i]:
+            continue
         e = fn(ptr(i), C.c_int(nf), dp(f[i]), dp(fc[i]), dp(fp), dp(mp[i]), dp(cm), dp(cc), dp(ci))
         if e:
             raise RuntimeError("oracle visual update failed: %s" % abi.STATUS.get(e, e))
 
 
-def _pose_update_visual(self, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in_imu):
+def _pose_update_visual(self, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in_imu,
+                        mask=None):
     """PoseUKF::integrateMeasurement(vector<VisualFeatureMeasurement>, ...) (PoseUKF.cpp:613-654)."""
     _pose_visual(self.L, self.L.or_pose_update_visual, self.ptr, self.batch, features, feature_cov, feature_pos,
-                 marker_pose, cov_marker, cam, cam_in_imu)
+                 marker_pose, cov_marker, cam, cam_in_imu, mask)
 
 
 OraclePoseBatch.update_visual = _pose_update_visual
@@ -428,9 +432,11 @@ class OracleBottomBatch(_SmallBatch):
             if e:
                 raise RuntimeError("oracle range update: %s" % abi.STATUS.get(e, e))
 
-    def update_normal(self, mu, cov):
+    def update_normal(self, mu, cov, mask=None):
         mu, cov = _per(mu, self.batch, (3,)), _per(cov, self.batch, (2, 2))
         for i in range(self.batch):
+            if mask is not None and not mask[i]:
+                continue
             e = self.L.or_bottom_update_normal(self.ptr(i), dp(mu[i]), dp(cov[i]))
             if e:
                 raise RuntimeError("oracle normal update: %s" % abi.STATUS.get(e, e))
@@ -469,9 +475,10 @@ class OracleIndirectPoseBatch(_SmallBatch):
             if e:
                 raise RuntimeError("oracle ipose predict: %s" % abi.STATUS.get(e, e))
 
-    def update_visual(self, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in_body):
+    def update_visual(self, features, feature_cov, feature_pos, marker_pose, cov_marker, cam, cam_in_body,
+                      mask=None):
         _pose_visual(self.L, self.L.or_ipose_update_visual, self.ptr, self.batch, features, feature_cov,
-                     feature_pos, marker_pose, cov_marker, cam, cam_in_body)
+                     feature_pos, marker_pose, cov_marker, cam, cam_in_body, mask)
 
     def get_corrected_pose(self):
         out = np.empty((self.batch, 7))

@@ -422,13 +422,16 @@ uwvk_status uwvk_bottom_update_normal(uwvk_bottom* h, const double* mu, const do
   if (!h || !mu || (!cov && !shared_cov)) return UWVK_EINVAL;
   if (!h->has_state) return UWVK_ENOTINIT;
   const int64_t B = h->batch;
-  // the reference does not check this measurement (BottomUKF.cpp:63-67); a
-  // zero / non-finite normal cannot be normalised into S2
+  // the reference does not check this measurement (BottomUKF.cpp:63-67); here a
+  // non-finite mean or covariance of a masked-in instance is UWVK_ENAN like every
+  // other measurement, and a zero normal cannot be normalised into S2
   for (int64_t i = 0; i < B; i++) {
     if (mask && !mask[i]) continue;
     const double* v = mu + i * 3;
-    if (!finite_all(v, 3) || !(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return UWVK_EINVAL;
+    if (!finite_all(v, 3) || (cov && !finite_all(cov + i * 4, 4))) return UWVK_ENAN;
+    if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return UWVK_EINVAL;
   }
+  if (!cov && !finite_all(shared_cov, 4)) return UWVK_ENAN;
   double* dz = h->d_meas;
   double* dc = h->d_meas + B * 3;
   HIPCHK(hipMemcpyAsync(dz, mu, (size_t)B * 3 * 8, hipMemcpyHostToDevice, h->stream));

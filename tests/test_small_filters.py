@@ -15,6 +15,7 @@ import visual_scene as V
 from helpers import cov_err, pose_setup, qlog_err, state_err
 from uwvk import engine, synth
 from uwvk.small import BottomUKFBatch, IndirectPoseUKFBatch
+from visual_scene import bottom_state, ipose_scene, pose_scene, visual_common
 
 L = O.lib()
 DP = O.DP
@@ -55,18 +56,6 @@ def test_s2_manifold_identities():
         ang = np.arccos(np.clip(np.dot(z, x), -1, 1))
         assert abs(np.linalg.norm(s2_minus(z, x)) - ang) < 1e-12
     np.testing.assert_allclose(s2_plus(np.array([0, 0, 1.0]), np.zeros(2)), [0, 0, 1.0], atol=0)
-
-
-def bottom_state(B, seed=5):
-    rng = np.random.default_rng(seed)
-    x = np.zeros((B, 4))
-    x[:, 0] = 10.0 + rng.uniform(-1, 1, B)
-    x[:, 1:] = _s2(np.c_[rng.normal(0, 0.1, (B, 2)), np.ones(B)])
-    P = np.zeros((B, 3, 3))
-    for i in range(B):
-        A = rng.normal(0, 1, (3, 3)) * [0.3, 0.05, 0.05]
-        P[i] = A @ A.T + np.diag([0.05, 0.003, 0.003])
-    return x, P
 
 
 def test_bottom_predict_is_exact_shift():
@@ -126,28 +115,6 @@ def test_ipose_predict_blocks():
     np.testing.assert_allclose(np.diag(P1[0])[3:], a * a * ori_std ** 2 + 2 * dt / tau * ori_std ** 2, rtol=1e-12)
 
 
-def ipose_scene(B, seed=11):
-    rng = np.random.default_rng(seed)
-    ref_t = rng.normal(0, 5, (B, 3))
-    ref_q = V.qexp(rng.normal(0, 0.3, (B, 3)))
-    p_err = rng.normal(0, 0.3, (B, 3))
-    q_err = V.qexp(rng.normal(0, 0.02, (B, 3)))
-    body_t = ref_t + V.qrot(ref_q, p_err)
-    body_q = V.qmul(ref_q, q_err)
-    marker = V.marker_ahead(body_t, body_q)
-    px, zc = V.project(body_t, body_q, marker)
-    assert (zc > 1.0).all()
-    px = px + V.pixel_noise(B, seed + 1, 0.3)
-    ref = np.concatenate([ref_t, ref_q], 1)
-    return ref, p_err, q_err, marker, px
-
-
-def visual_common(B):
-    fcov = np.tile(np.eye(2) * 0.09, (4, 1, 1))
-    cov_marker = np.diag([1e-4] * 3 + [1e-5] * 3)
-    return fcov, V.CORNERS, cov_marker, V.CAMERA, V.CAM_IN_BODY
-
-
 def test_ipose_visual_update_reduces_error():
     B = 6
     ref, p_err, q_err, marker, px = ipose_scene(B)
@@ -180,18 +147,6 @@ def test_ipose_visual_nan_feature_changes_nothing():
         o.update_visual(px, fcov, fpos, marker, cm, cam, cib)
     after = o.get_state()
     np.testing.assert_array_equal(before[0][0], after[0][0])
-
-
-def pose_scene(x, seed=21):
-    """marker ahead of each (perturbed) PoseUKF estimate; true pose = estimate + offset"""
-    B = len(x)
-    rng = np.random.default_rng(seed)
-    true_t = x[:, :3] + rng.normal(0, 0.2, (B, 3))
-    true_q = V.qmul(V.qexp(rng.normal(0, 0.01, (B, 3))), x[:, 3:7])
-    marker = V.marker_ahead(true_t, true_q)
-    px, zc = V.project(true_t, true_q, marker)
-    assert (zc > 1.0).all()
-    return true_t, true_q, marker, px + V.pixel_noise(B, seed + 1, 0.3)
 
 
 @pytest.mark.parametrize("right", [True, False])
