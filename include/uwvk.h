@@ -54,7 +54,8 @@ extern "C" {
  *      added within 3, purely additive (no existing struct, flag or entry
  *      point changed): uwvk_pose_fixes, UWVK_FIX_*, uwvk_pose_run_log_fixes,
  *      uwvk_schedule_fixes; uwvk_pose_delayed, uwvk_pose_run_log_delayed,
- *      uwvk_schedule_delayed. */
+ *      uwvk_schedule_delayed; uwvk_bottom_log, uwvk_bottom_track, UWVK_BEV_*,
+ *      uwvk_bottom_log_check, uwvk_bottom_run_log, uwvk_bottom_synchronize. */
 #define UWVK_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
@@ -841,6 +842,88 @@ uwvk_status uwvk_bottom_update_normal(uwvk_bottom* h, const double* mu, const do
                                       const uint8_t* mask);
 uwvk_status uwvk_bottom_get_state(uwvk_bottom* h, double* x, double* P);
 uwvk_status uwvk_bottom_get_status(uwvk_bottom* h, uint32_t* status, int clear);
+
+/* ---- BottomUKF in a run: a device-resident multi-epoch log --------------- */
+/* One epoch is one DVL ping: setVelocity, predictionStep(dt), the range
+ * updates of the beams that have a range, then the normal update if there is
+ * one.  One launch covers up to 4096 epochs with (mu, Sigma) resident in LDS. */
+#define UWVK_BOTTOM_MAX_BEAMS 8
+#define UWVK_BEV_BEAM(b)  (1u << (b))   /* b < beams: beam b has a range this epoch */
+#define UWVK_BEV_NORMAL   0x100u        /* a normal measurement this epoch */
+
+typedef struct uwvk_bottom_log {
+  int64_t epochs;
+  double dt;                       /* predict step (host value), > 0 */
+  const uint32_t* flags;           /* HOST [epochs] UWVK_BEV_* */
+  const double* velocity;          /* DEVICE [epochs][batch][3] (setVelocity of that epoch) */
+  int32_t beams;                   /* 0..UWVK_BOTTOM_MAX_BEAMS */
+  double beam_direction[UWVK_BOTTOM_MAX_BEAMS][3];  /* host, shared; unit_direction of beam b */
+  double beam_origin[UWVK_BOTTOM_MAX_BEAMS][3];     /* host, shared */
+  const int32_t* range_index;      /* HOST [epochs]: row into range where any beam bit is set */
+  const double* range;             /* DEVICE [n_range][beams][batch] */
+  const double* range_var;         /* DEVICE [n_range][beams][batch], NULL = range_cov for all */
+  int64_t n_range;
+  double range_cov;                /* host, shared */
+  const int32_t* normal_index;     /* HOST [epochs] */
+  const double* normal;            /* DEVICE [n_normal][batch][3], normalised by the filter */
+  int64_t n_normal;
+  double normal_cov[4];            /* host, shared */
+} uwvk_bottom_log;
+
+typedef struct uwvk_bottom_track {
+  int64_t every, capacity;         /* as uwvk_pose_track: a record after each absolute epoch e
+                                      with (e + 1) % every == 0; capacity in records */
+  double* mean;                    /* DEVICE [records][batch][4], nullable */
+  double* variance;                /* DEVICE [records][batch][3] diagonal of Sigma, nullable */
+} uwvk_bottom_track;
+
+/* host only, no device needed: the checks uwvk_bottom_run_log makes before it
+ * queues anything, over epochs [first, first + count).
+ * UWVK_EINVAL: log NULL; a negative range or one past log->epochs; dt not > 0;
+ * beams outside 0..UWVK_BOTTOM_MAX_BEAMS; a flag bit that is neither a beam
+ * below `beams` nor UWVK_BEV_NORMAL; flags or velocity NULL while count > 0; a
+ * flagged kind whose index or payload pointer is NULL; an index outside
+ * [0, n_kind) at a flagged epoch.
+ * UWVK_ENAN: a non-finite range_cov (when range_var is NULL), normal_cov, beam
+ * direction or beam origin that a flagged epoch of the range uses. */
+uwvk_status uwvk_bottom_log_check(const uwvk_bottom_log* log, int64_t first, int64_t count);
+
+/* Epochs [first, first + count) of the log.  Epoch e: velocity[e] becomes the
+ * handle's velocity; predict with dt; the range updates of the flagged beams in
+ * beam order 0..beams-1 (beam b's direction and origin, range_var if given,
+ * else range_cov); the normal update if flagged; a track record if e is a
+ * record epoch (numbered as uwvk_pose_track_records numbers them; a record does
+ * not end a launch).  Afterwards the handle's velocity is that of the last
+ * epoch, as after the single calls; the process noise is the handle's.
+ *
+ * The result is bitwise that of the single calls on the same handle state in
+ * this order: mu, Sigma, the status words, and every record against
+ * uwvk_bottom_get_state at that epoch.  Calls over adjacent ranges give bitwise
+ * what one call over the whole range gives.
+ *
+ * The payloads are in device memory, so what the single calls refuse on the
+ * host is handled per instance here:
+ *  - a non-finite range or variance: that update is skipped for that instance
+ *    and beam (the single call with the instance masked out), UWVK_ST_NAN;
+ *  - a non-finite or zero-length normal: skipped for that instance, UWVK_ST_NAN;
+ *  - a non-finite velocity: that instance skips the epoch's predict,
+ *    UWVK_ST_NAN, and its stored velocity keeps its last finite value;
+ *  - a step whose Cholesky meets a non-positive pivot (at the sigma spread or
+ *    in apply_delta's re-spread): (mu, Sigma) stays exactly as before that
+ *    step, UWVK_ST_NOTPD, and the later steps of the run still run on it.
+ * applied (DEVICE [batch][2], nullable, zeroed by the caller): the range and
+ * normal updates that changed the instance are added to it.
+ *
+ * Returns uwvk_bottom_log_check's result first, then UWVK_EINVAL for a track
+ * with every <= 0, both buffers NULL or capacity < uwvk_pose_track_records(
+ * first, count, every), all with nothing queued and the state untouched;
+ * UWVK_ENOTINIT before uwvk_bottom_init.
+ * Asynchronous on the handle's stream like uwvk_vel_run_log: the host arrays
+ * are copied before it returns; the getters and uwvk_bottom_synchronize wait. */
+uwvk_status uwvk_bottom_run_log(uwvk_bottom* h, const uwvk_bottom_log* log, int64_t first, int64_t count,
+                                uint32_t* applied /* DEVICE [batch][2] ranges, normals applied; nullable, caller zeroes */,
+                                const uwvk_bottom_track* track /* nullable */);
+uwvk_status uwvk_bottom_synchronize(uwvk_bottom* h);
 
 /* ======================================================================== */
 /* IndirectPoseUKF (src/IndirectPoseUKF.hpp:28-86, IndirectPoseUKF.cpp:1-147) */

@@ -8,6 +8,7 @@
 // 32 lanes (2 per wave).  Sigma lives in LDS for the duration of a call.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -76,22 +77,23 @@ __device__ E make_engine(double* smem, const SmallBufs& b, const uint8_t* mask, 
 }
 
 // ---- BottomUKF -----------------------------------------------------------
-// predictionStepImpl (BottomUKF.cpp:48-54) + processModel (:5-16)
-__global__ __launch_bounds__(BE::BLOCK) void k_bottom_predict(SmallBufs b, const double* vel, M9 Q, double dt) {
-  __shared__ double smem[BE::IPB * BE::words];
-  int64_t inst;
-  BE e = make_engine<BE>(smem, b, nullptr, &inst);
-  load(e, b, inst);
+// The three step bodies, on an engine whose (mu, Sigma) is in LDS.  The single
+// kernels and k_bottom_run both call them, so both compile the same
+// expressions: the run's bitwise contract (include/uwvk.h) rests on that.
+// The inputs of an instance are read only if it is e.live; predict and range
+// read them themselves, at row `at` of the caller's arrays.
+
+// predictionStepImpl (BottomUKF.cpp:48-54) + processModel (:5-16); vel: [..][3]
+UWVK_DEV bool bottom_predict_step(BE& e, const double* vel, int64_t at, const M9& Q, double dt) {
   double vz = 0.0, s = 0.0;
   if (e.live) {
-    const double vx = vel[inst * 3], vy = vel[inst * 3 + 1];
-    vz = vel[inst * 3 + 2];
+    const double vx = vel[at * 3], vy = vel[at * 3 + 1];
+    vz = vel[at * 3 + 2];
     const double nrm = sqrt(vx * vx + vy * vy);
     s = (nrm * nrm) * (dt * dt);  // pow(|v_xy|, 2) * pow(dt, 2)
   }
-  const bool ok = e.predict([&](double* x) { x[0] = x[0] + (-1.0 * vz) * dt; },
-                            [&](int r, int c) { return s * Q.v[r * 3 + c]; });
-  store(e, b, inst, ok);
+  return e.predict([&](double* x) { x[0] = x[0] + (-1.0 * vz) * dt; },
+                   [&](int r, int c) { return s * Q.v[r * 3 + c]; });
 }
 
 // measurementDistance (BottomUKF.cpp:18-30)
@@ -109,19 +111,13 @@ struct RangeH {
 
 // integrateMeasurement(RangeMeasurement, unit_direction, origin) (BottomUKF.cpp:56-61):
 // DistanceType (mtkwrap<Scalar>) measurement -> iterative vect mean
-__global__ __launch_bounds__(BE::BLOCK) void k_bottom_range(SmallBufs b, const double* z, const double* cov,
-                                                            double shared_cov, RangeH h, const uint8_t* mask) {
-  __shared__ double smem[BE::IPB * BE::words];
-  int64_t inst;
-  BE e = make_engine<BE>(smem, b, mask, &inst);
-  load(e, b, inst);
+UWVK_DEV bool bottom_range_step(BE& e, const double* z, const double* cov, double shared_cov, int64_t at, RangeH h) {
   double zz[3] = {0.0, 0.0, 0.0}, R[1] = {1.0};
   if (e.live) {
-    zz[0] = z[inst];
-    R[0] = cov ? cov[inst] : shared_cov;
+    zz[0] = z[at];
+    R[0] = cov ? cov[at] : shared_cov;
   }
-  const bool ok = e.template update<Z_VECT, 1>(zz, R, h);
-  store(e, b, inst, ok);
+  return e.template update<Z_VECT, 1>(zz, R, h);
 }
 
 // measurementNormal (BottomUKF.cpp:32-37)
@@ -129,21 +125,190 @@ struct NormalH {
   UWVK_DEV void operator()(const double* x, double* z) const { z[0] = x[1]; z[1] = x[2]; z[2] = x[3]; }
 };
 
-// integrateMeasurement(NormalType, cov) (BottomUKF.cpp:63-67): S2 measurement
+// integrateMeasurement(NormalType, cov) (BottomUKF.cpp:63-67): S2 measurement;
+// z: this instance's measured normal (normalised here), cov: its 2 x 2
+UWVK_DEV bool bottom_normal_step(BE& e, const double z[3], const double cov[4]) {
+  double zz[3] = {0.0, 0.0, 1.0}, R[4] = {1.0, 0.0, 0.0, 1.0};
+  if (e.live) {
+    s2_from(z, zz);
+#pragma unroll
+    for (int k = 0; k < 4; k++) R[k] = cov[k];
+  }
+  return e.template update<Z_S2, 2>(zz, R, NormalH{});
+}
+
+__global__ __launch_bounds__(BE::BLOCK) void k_bottom_predict(SmallBufs b, const double* vel, M9 Q, double dt) {
+  __shared__ double smem[BE::IPB * BE::words];
+  int64_t inst;
+  BE e = make_engine<BE>(smem, b, nullptr, &inst);
+  load(e, b, inst);
+  const bool ok = bottom_predict_step(e, vel, inst, Q, dt);
+  store(e, b, inst, ok);
+}
+
+__global__ __launch_bounds__(BE::BLOCK) void k_bottom_range(SmallBufs b, const double* z, const double* cov,
+                                                            double shared_cov, RangeH h, const uint8_t* mask) {
+  __shared__ double smem[BE::IPB * BE::words];
+  int64_t inst;
+  BE e = make_engine<BE>(smem, b, mask, &inst);
+  load(e, b, inst);
+  const bool ok = bottom_range_step(e, z, cov, shared_cov, inst, h);
+  store(e, b, inst, ok);
+}
+
 __global__ __launch_bounds__(BE::BLOCK) void k_bottom_normal(SmallBufs b, const double* z, const double* cov,
                                                              M9 shared_cov, const uint8_t* mask) {
   __shared__ double smem[BE::IPB * BE::words];
   int64_t inst;
   BE e = make_engine<BE>(smem, b, mask, &inst);
   load(e, b, inst);
-  double zz[3] = {0.0, 0.0, 1.0}, R[4] = {1.0, 0.0, 0.0, 1.0};
+  double zi[3] = {0.0, 0.0, 1.0}, R[4] = {1.0, 0.0, 0.0, 1.0};
   if (e.live) {
-    s2_from(z + inst * 3, zz);
+#pragma unroll
+    for (int k = 0; k < 3; k++) zi[k] = z[inst * 3 + k];
 #pragma unroll
     for (int k = 0; k < 4; k++) R[k] = cov ? cov[inst * 4 + k] : shared_cov.v[k];
   }
-  const bool ok = e.template update<Z_S2, 2>(zz, R, NormalH{});
+  const bool ok = bottom_normal_step(e, zi, R);
   store(e, b, inst, ok);
+}
+
+// ---- BottomUKF in a run (uwvk_bottom_run_log) -------------------------------
+// One launch covers up to kBottomChunk epochs: (mu, Sigma) is loaded once, stays
+// in the instance's LDS words across the epochs and is stored once.  The epoch
+// table is uniform over the grid, so every instance of a block takes the same
+// barrier sequence; what an instance skips (a non-finite payload) is the
+// engine's `live` flag of that step, as a masked-out instance of the single
+// kernels, never a branch around the step.
+constexpr int64_t kBottomChunk = 4096;        // epochs per launch, as uwvk_vel_run_log
+constexpr uint32_t kBevRecord = 0x80000000u;  // epoch table only: a track record follows this epoch
+struct BottomEpoch {                          // one row of the device epoch table
+  uint32_t flags;                             // UWVK_BEV_* | kBevRecord
+  int32_t range_row, normal_row, record;      // rows of the payloads, record of this call
+};
+struct BottomRunArgs {
+  const BottomEpoch* ev;   // DEVICE [count], this launch's epochs
+  int32_t count, beams;
+  const double* velocity;  // this launch's first epoch: [count][batch][3]
+  const double* range;     // [n_range][beams][batch]
+  const double* range_var; // nullable
+  const double* normal;    // [n_normal][batch][3]
+  double* vel_io;          // the handle's velocity [batch][3]: read at entry, written at exit
+  uint32_t* applied;       // [batch][2], nullable
+  double* tr_mean;         // [records][batch][4], nullable
+  double* tr_var;          // [records][batch][3], nullable
+  double dt, range_cov;
+  double normal_cov[4];
+  RangeH beam[UWVK_BOTTOM_MAX_BEAMS];
+  M9 Q;
+};
+
+UWVK_DEV bool finite_dev(double v) { return v - v == 0.0; }  // neither NaN nor Inf
+
+__global__ __launch_bounds__(BE::BLOCK) void k_bottom_run(SmallBufs b, BottomRunArgs a) {
+  __shared__ double smem[BE::IPB * BE::words];
+  int64_t inst;
+  BE e = make_engine<BE>(smem, b, nullptr, &inst);
+  const bool in = e.live;  // instance < batch
+  if (!in) {  // the tail of the last block: a valid state, so its (unused) steps converge at once
+    for (int i = e.g; i < BE::n * BE::n; i += BE::G) e.sm[BE::o_sig + i] = i % (BE::n + 1) == 0 ? 1.0 : 0.0;
+    for (int k = e.g; k < BE::S; k += BE::G) e.sm[BE::o_mu + k] = k == 0 || k == BE::S - 1 ? 1.0 : 0.0;
+  }
+  load(e, b, inst);
+  double v[3] = {0.0, 0.0, 0.0};
+  if (in) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) v[k] = a.vel_io[inst * 3 + k];
+  }
+  uint32_t st = 0, n_range = 0, n_normal = 0;
+  for (int32_t t = 0; t < a.count; t++) {
+    const BottomEpoch ev = a.ev[t];
+    // setVelocity + predictionStep
+    bool live = in;
+    if (in) {
+      const double* ve = a.velocity + ((int64_t)t * b.batch + inst) * 3;
+      const double nv[3] = {ve[0], ve[1], ve[2]};
+      if (finite_dev(nv[0]) && finite_dev(nv[1]) && finite_dev(nv[2])) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) v[k] = nv[k];
+      } else {
+        live = false;
+        st |= UWVK_ST_NAN;
+      }
+    }
+    e.live = live;
+    if (!bottom_predict_step(e, v, 0, a.Q, a.dt) && live) st |= UWVK_ST_NOTPD;
+    // the updates: Engine::update has already reduced Sigma in LDS when the
+    // Cholesky of apply_delta fails (mu is written last), so Sigma is kept in
+    // registers over each update (9 words over the group's 8 lanes) and put back
+    const int64_t rrow = (int64_t)ev.range_row * a.beams;
+    for (int32_t bm = 0; bm < a.beams; bm++) {
+      if (!(ev.flags & UWVK_BEV_BEAM(bm))) continue;  // uniform
+      live = in;
+      const int64_t at = (rrow + bm) * b.batch + inst;
+      if (in) {
+        const double z = a.range[at], var = a.range_var ? a.range_var[at] : a.range_cov;
+        if (!(finite_dev(z) && finite_dev(var))) {
+          live = false;
+          st |= UWVK_ST_NAN;
+        }
+      }
+      const double keep0 = e.sm[BE::o_sig + e.g], keep8 = e.sm[BE::o_sig + 8];
+      e.live = live;
+      const bool ok = bottom_range_step(e, a.range, a.range_var, a.range_cov, at, a.beam[bm]);
+      if (live && ok) n_range++;
+      if (live && !ok) {
+        st |= UWVK_ST_NOTPD;
+        e.sm[BE::o_sig + e.g] = keep0;
+        if (e.g == 0) e.sm[BE::o_sig + 8] = keep8;
+      }
+      __syncthreads();
+    }
+    if (ev.flags & UWVK_BEV_NORMAL) {  // uniform
+      live = in;
+      double zn[3] = {0.0, 0.0, 1.0};
+      if (in) {
+        const double* ne = a.normal + ((int64_t)ev.normal_row * b.batch + inst) * 3;
+        const double nv[3] = {ne[0], ne[1], ne[2]};
+        if (finite_dev(nv[0]) && finite_dev(nv[1]) && finite_dev(nv[2]) &&
+            nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2] > 0.0) {
+#pragma unroll
+          for (int k = 0; k < 3; k++) zn[k] = nv[k];
+        } else {
+          live = false;
+          st |= UWVK_ST_NAN;
+        }
+      }
+      const double keep0 = e.sm[BE::o_sig + e.g], keep8 = e.sm[BE::o_sig + 8];
+      e.live = live;
+      const bool ok = bottom_normal_step(e, zn, a.normal_cov);
+      if (live && ok) n_normal++;
+      if (live && !ok) {
+        st |= UWVK_ST_NOTPD;
+        e.sm[BE::o_sig + e.g] = keep0;
+        if (e.g == 0) e.sm[BE::o_sig + 8] = keep8;
+      }
+      __syncthreads();
+    }
+    // track record, straight from LDS (every step above ends in a barrier)
+    if ((ev.flags & kBevRecord) && in) {
+      const int64_t at = (int64_t)ev.record * b.batch + inst;
+      if (a.tr_mean && e.g < BE::S) a.tr_mean[at * BE::S + e.g] = e.sm[BE::o_mu + e.g];
+      if (a.tr_var && e.g < BE::n) a.tr_var[at * BE::n + e.g] = e.sm[BE::o_sig + e.g * BE::n + e.g];
+    }
+  }
+  e.live = in;
+  store(e, b, inst, true);
+  if (in) {
+    if (e.g < 3) a.vel_io[inst * 3 + e.g] = v[e.g];
+    if (e.g == 0) {
+      if (st) b.status[inst] |= st;
+      if (a.applied) {
+        a.applied[inst * 2] += n_range;
+        a.applied[inst * 2 + 1] += n_normal;
+      }
+    }
+  }
 }
 
 // ---- IndirectPoseUKF -------------------------------------------------------
@@ -245,9 +410,64 @@ struct SmallHandle {
   SmallBufs bufs() const { return SmallBufs{batch, d_mu, d_sigma, d_status}; }
 };
 
+// The epoch table of one uwvk_bottom_run_log call: written into pinned host
+// memory before the call returns, copied to the device on the handle's stream.
+// A slot is free again once the event behind its last launch has passed.
+struct BottomStage {
+  BottomEpoch* host = nullptr;  // pinned
+  BottomEpoch* dev = nullptr;
+  int64_t cap = 0;              // epochs
+  hipEvent_t done = nullptr;
+  bool used = false;
+};
+
 struct uwvk_bottom : SmallHandle {
   M9 Q{};
+  std::vector<BottomStage> stages;
 };
+
+static void bottom_release_stages(uwvk_bottom* h) {
+  for (BottomStage& s : h->stages) {
+    if (s.host) (void)hipHostFree(s.host);
+    if (s.dev) (void)hipFree(s.dev);
+    if (s.done) (void)hipEventDestroy(s.done);
+  }
+  h->stages.clear();
+}
+
+// a slot of at least `epochs` rows that no queued launch reads any more
+static BottomStage* bottom_stage(uwvk_bottom* h, int64_t epochs) {
+  BottomStage* s = nullptr;
+  for (BottomStage& c : h->stages)
+    if (!c.used || hipEventQuery(c.done) == hipSuccess) {
+      c.used = false;
+      if (!s) s = &c;
+    }
+  if (!s) {
+    h->stages.emplace_back();
+    s = &h->stages.back();
+    if (hipEventCreateWithFlags(&s->done, hipEventDisableTiming) != hipSuccess) {
+      s->done = nullptr;
+      h->stages.pop_back();
+      return nullptr;
+    }
+  }
+  if (s->cap < epochs) {
+    if (s->host) (void)hipHostFree(s->host);
+    if (s->dev) (void)hipFree(s->dev);
+    s->host = s->dev = nullptr;
+    s->cap = 0;
+    const int64_t cap = std::max<int64_t>(epochs, 1024);
+    if (hipHostMalloc((void**)&s->host, (size_t)cap * sizeof(BottomEpoch), hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void**)&s->dev, (size_t)cap * sizeof(BottomEpoch)) != hipSuccess) {
+      if (s->host) (void)hipHostFree(s->host);
+      s->host = s->dev = nullptr;
+      return nullptr;
+    }
+    s->cap = cap;
+  }
+  return s;
+}
 struct uwvk_ipose : SmallHandle {
   M36 Q{};
   double tau = 1.0;
@@ -333,7 +553,8 @@ uwvk_status uwvk_bottom_create(int64_t batch, int device, uwvk_bottom** out) {
 void uwvk_bottom_destroy(uwvk_bottom* h) {
   UWVK_DEVICE_GUARD(h);
   if (!h) return;
-  small_destroy(h);
+  small_destroy(h);  // waits for the stream first
+  bottom_release_stages(h);
   delete h;
 }
 
@@ -443,6 +664,107 @@ uwvk_status uwvk_bottom_update_normal(uwvk_bottom* h, const double* mu, const do
   hipLaunchKernelGGL(k_bottom_normal, dim3(grid_of(B, BE::IPB)), dim3(BE::BLOCK), 0, h->stream, h->bufs(), dz,
                      cov ? dc : nullptr, sc, dm);
   HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return UWVK_OK;
+}
+
+// host only (no HIP call): what uwvk_bottom_run_log checks before it queues anything
+uwvk_status uwvk_bottom_log_check(const uwvk_bottom_log* log, int64_t first, int64_t count) {
+  if (!log || first < 0 || count < 0 || first > log->epochs || count > log->epochs - first) return UWVK_EINVAL;
+  if (!(log->dt > 0.0)) return UWVK_EINVAL;
+  if (log->beams < 0 || log->beams > UWVK_BOTTOM_MAX_BEAMS) return UWVK_EINVAL;
+  if (count > 0 && (!log->flags || !log->velocity)) return UWVK_EINVAL;
+  const uint32_t beam_bits = (1u << log->beams) - 1u;
+  uint32_t used = 0;
+  for (int64_t e = first; e < first + count; e++) {
+    const uint32_t f = log->flags[e];
+    if (f & ~(beam_bits | UWVK_BEV_NORMAL)) return UWVK_EINVAL;
+    if (f & beam_bits) {
+      if (!log->range_index || !log->range) return UWVK_EINVAL;
+      if (log->range_index[e] < 0 || log->range_index[e] >= log->n_range) return UWVK_EINVAL;
+    }
+    if (f & UWVK_BEV_NORMAL) {
+      if (!log->normal_index || !log->normal) return UWVK_EINVAL;
+      if (log->normal_index[e] < 0 || log->normal_index[e] >= log->n_normal) return UWVK_EINVAL;
+    }
+    used |= f;
+  }
+  // the shared host values the flagged epochs use (checkMeasurment of the single calls)
+  if ((used & beam_bits) && !log->range_var && !std::isfinite(log->range_cov)) return UWVK_ENAN;
+  for (int b = 0; b < log->beams; b++)
+    if ((used & UWVK_BEV_BEAM(b)) && (!finite_all(log->beam_direction[b], 3) || !finite_all(log->beam_origin[b], 3)))
+      return UWVK_ENAN;
+  if ((used & UWVK_BEV_NORMAL) && !finite_all(log->normal_cov, 4)) return UWVK_ENAN;
+  return UWVK_OK;
+}
+
+uwvk_status uwvk_bottom_run_log(uwvk_bottom* h, const uwvk_bottom_log* log, int64_t first, int64_t count,
+                                uint32_t* applied, const uwvk_bottom_track* track) {
+  UWVK_DEVICE_GUARD(h);
+  if (!h) return UWVK_EINVAL;
+  const uwvk_status chk = uwvk_bottom_log_check(log, first, count);
+  if (chk != UWVK_OK) return chk;
+  if (track && (track->every <= 0 || (!track->mean && !track->variance) ||
+                track->capacity < uwvk_pose_track_records(first, count, track->every)))
+    return UWVK_EINVAL;
+  if (!h->has_state) return UWVK_ENOTINIT;
+  if (count == 0) return UWVK_OK;
+  BottomStage* sg = bottom_stage(h, count);
+  if (!sg) return UWVK_ENOMEM;
+  const uint32_t beam_bits = (1u << log->beams) - 1u;
+  int32_t record = 0;
+  for (int64_t k = 0; k < count; k++) {
+    const int64_t e = first + k;
+    BottomEpoch& ev = sg->host[k];
+    ev.flags = log->flags[e];
+    ev.range_row = (ev.flags & beam_bits) ? log->range_index[e] : 0;
+    ev.normal_row = (ev.flags & UWVK_BEV_NORMAL) ? log->normal_index[e] : 0;
+    ev.record = 0;
+    if (track && (e + 1) % track->every == 0) {
+      ev.flags |= kBevRecord;
+      ev.record = record++;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(sg->dev, sg->host, (size_t)count * sizeof(BottomEpoch), hipMemcpyHostToDevice, h->stream));
+  sg->used = true;
+  BottomRunArgs a{};
+  a.beams = log->beams;
+  a.range = log->range;
+  a.range_var = log->range_var;
+  a.normal = log->normal;
+  a.vel_io = h->d_aux;
+  a.applied = applied;
+  a.tr_mean = track ? track->mean : nullptr;
+  a.tr_var = track ? track->variance : nullptr;
+  a.dt = log->dt;
+  a.range_cov = log->range_cov;
+  std::memcpy(a.normal_cov, log->normal_cov, sizeof(a.normal_cov));
+  for (int b = 0; b < log->beams; b++)
+    for (int k = 0; k < 3; k++) {
+      a.beam[b].dir[k] = log->beam_direction[b][k];
+      a.beam[b].origin[k] = log->beam_origin[b][k];
+    }
+  a.Q = h->Q;
+  // one launch per chunk of epochs; the state's round trip through HBM is exact
+  uwvk_status st = UWVK_OK;
+  for (int64_t k = 0; k < count && st == UWVK_OK; k += kBottomChunk) {
+    a.ev = sg->dev + k;
+    a.count = (int32_t)std::min<int64_t>(kBottomChunk, count - k);
+    a.velocity = log->velocity + (first + k) * h->batch * 3;
+    hipLaunchKernelGGL(k_bottom_run, dim3(grid_of(h->batch, BE::IPB)), dim3(BE::BLOCK), 0, h->stream, h->bufs(), a);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) st = (uwvk_status)::uwvk::edevice_status(le, "k_bottom_run");
+  }
+  if (hipEventRecord(sg->done, h->stream) != hipSuccess) {  // cannot tell when the slot is free: wait now
+    (void)hipStreamSynchronize(h->stream);
+    sg->used = false;
+  }
+  return st;
+}
+
+uwvk_status uwvk_bottom_synchronize(uwvk_bottom* h) {
+  UWVK_DEVICE_GUARD(h);
+  if (!h) return UWVK_EINVAL;
   HIPCHK(hipStreamSynchronize(h->stream));
   return UWVK_OK;
 }

@@ -55,6 +55,16 @@ class BottomUKF {
                                     measurement_cov.data(), m.mask.empty() ? nullptr : m.mask.data()),
           "integrateMeasurement(NormalType)");
   }
+  // Epochs [first, first + count) of a device-resident log (uwvk_bottom_run_log):
+  // per epoch setVelocity, predictionStep(log.dt), the flagged beams' range
+  // updates in beam order, the normal update; bitwise that call sequence.
+  // Asynchronous on the filter's stream: getState and synchronize wait.
+  // applied: DEVICE [batch][2] uint32, zeroed by the caller (nullable).
+  void runLog(const uwvk_bottom_log& log, int64_t first, int64_t count, uint32_t* applied = nullptr,
+              const uwvk_bottom_track* track = nullptr) {
+    check(uwvk_bottom_run_log(h_, &log, first, count, applied, track), "runLog");
+  }
+  void synchronize() { check(uwvk_bottom_synchronize(h_), "synchronize"); }
   void getState(std::vector<double>& x, std::vector<double>* P = nullptr) {
     x.resize((size_t)batch_ * 4);
     if (P) P->resize((size_t)batch_ * 9);

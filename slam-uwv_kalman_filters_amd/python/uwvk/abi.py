@@ -97,6 +97,25 @@ class VelLog(C.Structure):  # uwvk_vel_log (device pointers)
                 ("pressure_index", P), ("pressure", P), ("pressure_cov", D)]
 
 
+BOTTOM_MAX_BEAMS = 8   # UWVK_BOTTOM_MAX_BEAMS
+BEV_NORMAL = 0x100     # UWVK_BEV_NORMAL
+
+
+def bev_beam(b):       # UWVK_BEV_BEAM(b)
+    return 1 << b
+
+
+class BottomLog(C.Structure):  # uwvk_bottom_log (flags / indices host, payloads device)
+    _fields_ = [("epochs", C.c_int64), ("dt", D), ("flags", P), ("velocity", P), ("beams", C.c_int32),
+                ("beam_direction", _arr(D, 3 * BOTTOM_MAX_BEAMS)), ("beam_origin", _arr(D, 3 * BOTTOM_MAX_BEAMS)),
+                ("range_index", P), ("range", P), ("range_var", P), ("n_range", C.c_int64), ("range_cov", D),
+                ("normal_index", P), ("normal", P), ("n_normal", C.c_int64), ("normal_cov", _arr(D, 4))]
+
+
+class BottomTrack(C.Structure):  # uwvk_bottom_track (device buffers)
+    _fields_ = [("every", C.c_int64), ("capacity", C.c_int64), ("mean", P), ("variance", P)]
+
+
 class StreamTimes(C.Structure):  # uwvk_stream_times (host pointers)
     _fields_ = [("imu", P), ("n_imu", C.c_int64), ("dvl", P), ("n_dvl", C.c_int64),
                 ("pressure", P), ("n_pressure", C.c_int64), ("adcp", P), ("n_adcp", C.c_int64),

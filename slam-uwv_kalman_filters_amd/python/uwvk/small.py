@@ -2,12 +2,18 @@
 (IndirectPoseUKF.hpp:28-86) over the C ABI (uwvk_bottom_* / uwvk_ipose_*).
 
 Like the rest of the package there is no CPU fallback: construction raises
-UWVKError(UWVK_EDEVICE) without a gfx950 device."""
+UWVKError(UWVK_EDEVICE) without a gfx950 device.
+
+BottomUKFBatch.run_log runs a device-resident multi-epoch log
+(uwvk_bottom_run_log, DeviceBottomLog); BottomLogRecorder turns a call sequence
+into such a log's host arrays and play_bottom_log issues a host log as single
+calls to any filter object (both pure Python, no device)."""
 import ctypes as C
 
 import numpy as np
 
-from .engine import VP, _chk, _f64, _p, lib, visual_args
+from . import abi
+from .engine import VP, DeviceBuffer, _chk, _f64, _p, lib, visual_args
 
 
 def _per(a, batch, tail):
@@ -92,6 +98,232 @@ class BottomUKFBatch(_Small):
         sc = _f64(cv) if shared else None
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         _chk(self._fn("update_normal")(self.h, _p(mu), _p(cvp), _p(sc), _p(m)), "bottom_update_normal")
+
+    @property
+    def stream(self):
+        f = self._fn("stream")
+        f.restype, f.argtypes = VP, [VP]
+        return VP(f(self.h))
+
+    def upload_log(self, log):
+        return DeviceBottomLog(log, self.device)
+
+    def synchronize(self):
+        _chk(self._fn("synchronize")(self.h), "bottom_synchronize")
+
+    def run_log(self, dlog, first=0, count=None, every=None, sync=True, applied=None, capacity=None, mean=True,
+                variance=True):
+        """Epochs [first, first + count) of a DeviceBottomLog in one launch per 4096
+        epochs (uwvk_bottom_run_log): per epoch set_velocity, predict(dt), the
+        flagged beams' range updates in beam order, the normal update.  Bitwise
+        the single calls (play_bottom_log on this class).  applied: a
+        DeviceBuffer of [batch][2] uint32 the applied range / normal updates are
+        added to.  every: a record after each absolute epoch e with
+        (e + 1) % every == 0; returns (mean [records][batch][4], variance
+        [records][batch][3]) (None for one switched off), read back after the run."""
+        if dlog.batch != self.batch:
+            raise ValueError("log of batch %d on a filter of batch %d" % (dlog.batch, self.batch))
+        count = dlog.epochs - first if count is None else count
+        ap = applied.ptr if applied is not None else None
+        tr, bufs, n = None, {}, 0
+        if every is not None:
+            n = int(self.L.uwvk_pose_track_records(C.c_int64(first), C.c_int64(count), C.c_int64(every)))
+            cap = n if capacity is None else int(capacity)
+            bufs["mean"] = DeviceBuffer.empty(cap * self.batch * 4 * 8, self.device) if mean else None
+            bufs["variance"] = DeviceBuffer.empty(cap * self.batch * 3 * 8, self.device) if variance else None
+            t = abi.BottomTrack()
+            t.every, t.capacity = int(every), cap
+            t.mean, t.variance = (bufs[k].ptr if bufs[k] else None for k in ("mean", "variance"))
+            tr = C.byref(t)
+        _chk(self._fn("run_log")(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count), ap, tr),
+             "bottom_run_log")
+        if sync:
+            self.synchronize()
+        if every is None:
+            return None
+        out = []
+        for name, w in (("mean", 4), ("variance", 3)):
+            b = bufs[name]
+            out.append(None if b is None else
+                       (b.read(np.float64, (n, self.batch, w), self.stream) if n else np.empty((0, self.batch, w))))
+        return tuple(out)
+
+
+def bottom_log_struct(log, ptr):
+    """abi.BottomLog of a host log (BottomLogRecorder.log()'s layout).  ptr: the
+    addresses of its DEVICE arrays {velocity, range, range_var, normal} (None:
+    absent).  Returns (struct, the host arrays it points into: keep them alive)."""
+    s = abi.BottomLog()
+    s.epochs, s.dt, s.beams = int(log["epochs"]), float(log["dt"]), int(log["beams"])
+    keep = {k: np.ascontiguousarray(log[k], dtype=t) for k, t in
+            (("flags", np.uint32), ("range_index", np.int32), ("normal_index", np.int32))}
+    s.flags, s.range_index, s.normal_index = (_p(keep[k]) for k in ("flags", "range_index", "normal_index"))
+    nb = min(s.beams, abi.BOTTOM_MAX_BEAMS) if s.beams > 0 else 0
+    abi.fill(s.beam_direction, np.asarray(log["beam_direction"], float).reshape(-1)[:3 * nb])
+    abi.fill(s.beam_origin, np.asarray(log["beam_origin"], float).reshape(-1)[:3 * nb])
+    s.velocity, s.range, s.range_var, s.normal = (ptr.get(k) for k in ("velocity", "range", "range_var", "normal"))
+    s.n_range, s.n_normal = len(log["range"]), len(log["normal"])
+    s.range_cov = float(log["range_cov"])
+    abi.fill(s.normal_cov, np.asarray(log["normal_cov"], float).reshape(-1))
+    return s, keep
+
+
+class DeviceBottomLog:
+    """uwvk_bottom_log: the payloads (velocity, range, range_var, normal) in
+    device memory, flags and row indices on the host.  `log` is a dict in
+    BottomLogRecorder.log()'s layout."""
+
+    def __init__(self, log, device=0):
+        self.bufs, ptr = {}, {}
+        for name in ("velocity", "range", "range_var", "normal"):
+            if log.get(name) is not None:
+                self.bufs[name] = DeviceBuffer(np.ascontiguousarray(log[name], dtype=np.float64), device)
+                ptr[name] = self.bufs[name].ptr
+        self.s, self.host = bottom_log_struct(log, ptr)
+        self.epochs = self.s.epochs
+        self.batch = int(np.asarray(log["velocity"]).shape[1])
+
+
+class BottomLogRecorder:
+    """Turns a call sequence on the oracle wrapper's BottomUKF methods into the
+    host arrays of a uwvk_bottom_log (no device).  Each predict opens an epoch
+    with the velocity last set; a new (direction, origin) pair appends a beam.
+    What the log cannot express raises ValueError: a dt that changes, a mask, an
+    update before the first predict, a per-instance normal covariance or one
+    that changes, a ninth beam, a beam updated twice or out of beam order within
+    an epoch, a range after the epoch's normal."""
+
+    def __init__(self, batch, dt):
+        self.batch, self.dt = int(batch), float(dt)
+        self.v = np.zeros((self.batch, 3))
+        self.beams = []          # (direction, origin)
+        self.epochs = []         # dict(v=, ranges={beam: (z, var, shared)}, normal=)
+        self.normal_cov = None
+
+    def set_velocity(self, v):
+        self.v = np.array(_per(v, self.batch, (3,)))
+
+    def predict(self, dt):
+        if float(dt) != self.dt:
+            raise ValueError("predict(%r) in a log of dt = %r" % (dt, self.dt))
+        self.epochs.append(dict(v=self.v, ranges={}, normal=None))
+
+    def _open(self, mask):
+        if mask is not None:
+            raise ValueError("a mask cannot be recorded")
+        if not self.epochs:
+            raise ValueError("an update before the first predict")
+        return self.epochs[-1]
+
+    def update_range(self, mu, cov, direction, origin, mask=None):
+        ep = self._open(mask)
+        d, o = np.array(direction, float).reshape(3), np.array(origin, float).reshape(3)
+        b = next((k for k, (bd, bo) in enumerate(self.beams) if (bd == d).all() and (bo == o).all()), None)
+        if b is None:
+            if len(self.beams) == abi.BOTTOM_MAX_BEAMS:
+                raise ValueError("more than %d beams" % abi.BOTTOM_MAX_BEAMS)
+            b = len(self.beams)
+        if ep["normal"] is not None:
+            raise ValueError("a range update after the epoch's normal update")
+        if ep["ranges"] and b <= max(ep["ranges"]):
+            raise ValueError("beam %d updated twice or out of beam order in one epoch" % b)
+        if b == len(self.beams):
+            self.beams.append((d, o))
+        cv = np.asarray(cov, np.float64)
+        ep["ranges"][b] = (np.array(_per(mu, self.batch, ())), np.array(_per(cv, self.batch, ())), cv.ndim == 0)
+
+    def update_normal(self, mu, cov, mask=None):
+        ep = self._open(mask)
+        cv = np.asarray(cov, np.float64)
+        if cv.shape != (2, 2):
+            raise ValueError("a per-instance normal covariance")
+        if self.normal_cov is not None and not (self.normal_cov == cv).all():
+            raise ValueError("the normal covariance changes")
+        if ep["normal"] is not None:
+            raise ValueError("two normal updates in one epoch")
+        self.normal_cov = cv.copy()
+        ep["normal"] = np.array(_per(mu, self.batch, (3,)))
+
+    def log(self):
+        E, B, nb = len(self.epochs), self.batch, len(self.beams)
+        flags = np.zeros(E, np.uint32)
+        ri, ni = np.zeros(E, np.int32), np.zeros(E, np.int32)
+        vel = np.zeros((E, B, 3))
+        rows, nrm = [], []
+        calls = [r for ep in self.epochs for r in ep["ranges"].values()]
+        scalars = {float(r[1][0]) for r in calls if r[2]}
+        shared = all(r[2] for r in calls) and len(scalars) <= 1  # one scalar covariance throughout
+        for e, ep in enumerate(self.epochs):
+            vel[e] = ep["v"]
+            if ep["ranges"]:
+                z, var = np.zeros((nb, B)), np.ones((nb, B))
+                for b, (zi, ci, _) in ep["ranges"].items():
+                    flags[e] |= abi.bev_beam(b)
+                    z[b], var[b] = zi, ci
+                ri[e] = len(rows)
+                rows.append((z, var))
+            if ep["normal"] is not None:
+                flags[e] |= abi.BEV_NORMAL
+                ni[e] = len(nrm)
+                nrm.append(ep["normal"])
+        return dict(
+            epochs=E, dt=self.dt, flags=flags, velocity=vel, beams=nb,
+            beam_direction=np.array([b[0] for b in self.beams]).reshape(nb, 3),
+            beam_origin=np.array([b[1] for b in self.beams]).reshape(nb, 3),
+            range_index=ri, range=np.array([r[0] for r in rows]).reshape(len(rows), nb, B),
+            range_var=None if shared else np.array([r[1] for r in rows]).reshape(len(rows), nb, B),
+            range_cov=scalars.pop() if shared and scalars else 0.0,
+            normal_index=ni, normal=np.array(nrm).reshape(len(nrm), B, 3),
+            normal_cov=np.eye(2) if self.normal_cov is None else self.normal_cov)
+
+
+def play_bottom_log(filt, log, first=0, count=None):
+    """The single calls of epochs [first, first + count) of a host log on any
+    filter with the oracle wrapper's methods, in uwvk_bottom_run_log's order, the
+    non-finite entries masked as the run skips them: a non-finite range or
+    variance masks that instance out of that beam's update, a non-finite or
+    zero-length normal out of the normal update (a filter that gets a mask must
+    take the `mask` keyword).  A non-finite velocity has no single-call form
+    (predict takes no mask): ValueError.  Returns [batch][2], the range and
+    normal updates issued to each instance."""
+    E = int(log["epochs"])
+    count = E - first if count is None else count
+    B = np.asarray(log["velocity"]).shape[1]
+    issued = np.zeros((B, 2), np.int64)
+    rv = log.get("range_var")
+    for e in range(first, first + count):
+        v = np.asarray(log["velocity"][e], float)
+        if not np.isfinite(v).all():
+            raise ValueError("epoch %d: a non-finite velocity cannot be played with single calls" % e)
+        filt.set_velocity(v)
+        filt.predict(float(log["dt"]))
+        f = int(log["flags"][e])
+        for b in range(int(log["beams"])):
+            if not f & abi.bev_beam(b):
+                continue
+            row = int(log["range_index"][e])
+            z = np.array(log["range"][row][b], float)
+            good = np.isfinite(z)
+            if rv is not None:
+                cov = np.array(rv[row][b], float)
+                good &= np.isfinite(cov)
+                cov[~good] = 1.0
+            else:
+                cov = float(log["range_cov"])
+            z[~good] = 0.0
+            kw = {} if good.all() else dict(mask=good)
+            filt.update_range(z, cov, log["beam_direction"][b], log["beam_origin"][b], **kw)
+            issued[:, 0] += good
+        if f & abi.BEV_NORMAL:
+            n = np.array(log["normal"][int(log["normal_index"][e])], float)
+            good = np.isfinite(n).all(axis=1)
+            with np.errstate(invalid="ignore", over="ignore"):
+                good &= (n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2]) > 0.0
+            n[~good] = [0.0, 0.0, 1.0]
+            kw = {} if good.all() else dict(mask=good)
+            filt.update_normal(n, np.asarray(log["normal_cov"], float).reshape(2, 2), **kw)
+            issued[:, 1] += good
+    return issued
 
 
 class IndirectPoseUKFBatch(_Small):
