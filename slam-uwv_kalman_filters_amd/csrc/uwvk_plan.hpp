@@ -1,12 +1,15 @@
 // uwvk_plan.hpp — the host planning of uwvk_pose_run_log, as pure functions of
 // integers and host arrays (plain C++17, no HIP): which epoch kernel a handle
-// runs, how a log range splits into launches, the grid and tail layout of one
-// launch, and the process-noise tables.  uwvk_pose.hip does the copies and the
-// launches; tests/cpp/plan_test.cpp, track_plan_test.cpp, fix_plan_test.cpp and
+// runs, the one launch list of a call (plan_run: epochs, BodyEfforts, position
+// fixes, latches and track records), the checks of the fix and delayed
+// arguments, the grid and tail layout of one launch, and the process-noise
+// tables.  uwvk_pose.hip does the copies and walks the list;
+// tests/cpp/plan_test.cpp, track_plan_test.cpp, fix_plan_test.cpp and
 // delayed_plan_test.cpp check this file on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "../../include/uwvk.h"
@@ -150,10 +153,10 @@ inline bool runs_pair(const EpochFacts& f) {
   return f.dof == 26 ? f.q_simple : runs_pd(f);
 }
 
-enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EFFORTS, FIX, LATCH };
+enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EPOCH_DENSE, EFFORTS, FIX, LATCH, RECORD };
 struct Launch {
   LaunchKind kind;
-  int64_t first, count;  // absolute epochs [first, first + count); EFFORTS, FIX, LATCH: the one epoch
+  int64_t first, count;  // absolute epochs [first, first + count); all but EPOCH_ONE / EPOCH_PAIR: the one epoch
   int pd;                // EPOCH_*: the parameter-decoupled form
   int vo;                // EFFORTS: the velocity-only form (UWVK_EV_EFFORTS_VELOCITY_ONLY)
   uint32_t ev_any;       // the OR of the epochs' flags (the kernel instantiation)
@@ -224,94 +227,119 @@ inline EpochPlan plan_epochs(const uint32_t* host_flags, int64_t first, int64_t 
 inline int64_t track_records(int64_t first, int64_t count, int64_t every) {
   return (first + count) / every - first / every;
 }
-// [first, first + count) cut after every record epoch: the segments tile the
-// range in order, each ends at a record epoch (record) or, the last one, at the
-// range's end without one.  Each segment is planned by plan_epochs on its own,
-// so a tracked run is the untracked runs of its segments, launch for launch.
-struct TrackSegment {
-  int64_t first, count;
-  bool record;
-};
-inline std::vector<TrackSegment> track_segments(int64_t first, int64_t count, int64_t every) {
-  std::vector<TrackSegment> s;
-  const int64_t end = first + count;
-  for (int64_t e = first; e < end;) {
-    const int64_t next = (e / every + 1) * every;  // one past the next record epoch
-    const bool record = next <= end;
-    const int64_t stop = record ? next : end;
-    s.push_back({e, stop - e, record});
-    e = stop;
-  }
-  return s;
-}
 
-// Position fixes (uwvk_pose_run_log_fixes): [first, first + count) is cut after
-// every epoch whose fix flags (UWVK_FIX_*) are non-zero.  Each piece is planned
-// by plan_epochs on its own, pdec carried from piece to piece, so a run with
-// fixes is the runs of its pieces, launch for launch; a piece that ends in a
-// fix epoch is followed by one FIX launch of that epoch (count 1, ev_any the
-// UWVK_FIX_* mask), after the piece's EFFORTS launch if the epoch has one (the
-// fixes are the last updates of an epoch).  A fix is linear in the position
-// rows and leaves the parameter block decoupled: pd / pair go on after it.
-// fix_flags: those of epochs first .. first + count - 1, or null (none): then,
-// and with all of them zero, the plan is plan_epochs' plan.
-inline EpochPlan plan_fix_epochs(const uint32_t* host_flags, const uint32_t* fix_flags, int64_t first, int64_t count,
-                                 EpochFacts f) {
-  EpochPlan p;
-  p.pdec = f.pdec;
-  const int64_t end = first + count;
-  for (int64_t e = first; e < end;) {
-    int64_t stop = e;
-    while (stop < end && !(fix_flags && fix_flags[stop - first])) stop++;
-    const bool fix = stop < end;
-    if (fix) stop++;  // the piece includes its fix epoch
-    const EpochPlan piece = plan_epochs(host_flags + (e - first), e, stop - e, f);
-    p.launches.insert(p.launches.end(), piece.launches.begin(), piece.launches.end());
-    f.pdec = p.pdec = piece.pdec;
-    if (fix) p.launches.push_back({FIX, stop - 1, 1, 0, 0, fix_flags[stop - 1 - first]});
-    e = stop;
-  }
-  return p;
-}
-
-// Delayed XY (uwvk_pose_run_log_delayed).  delayed_flags: per epoch of the range
-// (or null: none) two internal bits, built by run_log from uwvk_pose_delayed's
-// index and latch_epoch arrays; they lie outside UWVK_FIX_*, so a FIX launch's
-// mask can hold the fix kinds and the arrival bit.
+// Delayed XY (uwvk_pose_run_log_delayed): per epoch two internal bits, made by
+// delayed_events (below) from uwvk_pose_delayed's index and latch_epoch arrays;
+// they lie outside UWVK_FIX_*, so a FIX launch's mask can hold the fix kinds
+// and the arrival bit.
 constexpr uint32_t kDelayedArrive = 0x8u;  // a delayed row arrives at this epoch (its update runs)
 constexpr uint32_t kDelayedLatch = 0x10u;  // rows latch the position after this epoch's updates
-// A piece ends after any epoch with a fix flag, an arrival or a latch; each
-// piece is planned by plan_epochs on its own, pdec carried over, as in
-// plan_fix_epochs.  After the piece (and its EFFORTS launch if the epoch has
-// one): one FIX launch if the epoch has fixes or an arrival (ev_any the fix
-// kinds plus kDelayedArrive: the delayed update is the last of the epoch's
-// position updates, in the same launch), then one LATCH launch (ev_any
-// kDelayedLatch) if rows latch there, so a latch sees all updates of its epoch.
-// A delayed update is linear in the position rows like the other fixes: pd /
-// pair go on.  With null or all-zero delayed_flags the plan is plan_fix_epochs'.
-inline EpochPlan plan_delayed_epochs(const uint32_t* host_flags, const uint32_t* fix_flags,
-                                     const uint32_t* delayed_flags, int64_t first, int64_t count, EpochFacts f) {
+
+// The launch list of one run_log call, in stream order.  One rule: the range
+// [first, first + count) is cut after every epoch with an event (a fix flag,
+// an arrival, a latch, or a track record: (e + 1) % every == 0); each piece is
+// planned by plan_epochs on its own, pdec carried from piece to piece; then the
+// epoch's events follow the piece (and its EFFORTS launch, if the epoch has
+// one) in the order of uwvk.h: one FIX launch if the epoch has fixes or an
+// arrival (ev_any the UWVK_FIX_* kinds plus kDelayedArrive: the delayed update
+// is the last position update, in the same launch), one LATCH (the latch sees
+// all updates of its epoch), one RECORD.  So a call with events is the calls
+// of its pieces, launch for launch, and without events it is plan_epochs' plan.
+// The position updates are linear in the position rows and leave the
+// parameter block decoupled: pd / pair go on after them.
+// A dense handle (the literal kernels) runs one fused EPOCH_DENSE launch per
+// epoch instead, its efforts update included (no EFFORTS launch; host_flags is
+// not read), and is never parameter-decoupled afterwards.
+// host_flags, fix_flags, delayed_flags: those of epochs first .. first + count
+// - 1, the last two or null (none); every: the track's stride, or 0 (no track)
+inline EpochPlan plan_run(const uint32_t* host_flags, const uint32_t* fix_flags, const uint32_t* delayed_flags,
+                          int64_t every, int64_t first, int64_t count, EpochFacts f) {
   EpochPlan p;
+  if (f.dense) f.pdec = false;
   p.pdec = f.pdec;
   const int64_t end = first + count;
   auto fixes = [&](int64_t k) { return fix_flags ? fix_flags[k - first] : 0u; };
   auto delayed = [&](int64_t k) { return delayed_flags ? delayed_flags[k - first] & (kDelayedArrive | kDelayedLatch) : 0u; };
+  auto record = [&](int64_t k) { return every > 0 && (k + 1) % every == 0; };
   for (int64_t e = first; e < end;) {
     int64_t stop = e;
-    while (stop < end && !(fixes(stop) || delayed(stop))) stop++;
+    while (stop < end && !(fixes(stop) || delayed(stop) || record(stop))) stop++;
     const bool event = stop < end;
     if (event) stop++;  // the piece includes its event epoch
-    const EpochPlan piece = plan_epochs(host_flags + (e - first), e, stop - e, f);
-    p.launches.insert(p.launches.end(), piece.launches.begin(), piece.launches.end());
-    f.pdec = p.pdec = piece.pdec;
+    if (f.dense) {
+      for (int64_t k = e; k < stop; k++) p.launches.push_back({EPOCH_DENSE, k, 1, 0, 0, 0});
+    } else {
+      const EpochPlan piece = plan_epochs(host_flags + (e - first), e, stop - e, f);
+      p.launches.insert(p.launches.end(), piece.launches.begin(), piece.launches.end());
+      f.pdec = p.pdec = piece.pdec;
+    }
     if (event) {
-      const uint32_t fix = fixes(stop - 1) | (delayed(stop - 1) & kDelayedArrive);
-      if (fix) p.launches.push_back({FIX, stop - 1, 1, 0, 0, fix});
-      if (delayed(stop - 1) & kDelayedLatch) p.launches.push_back({LATCH, stop - 1, 1, 0, 0, kDelayedLatch});
+      const int64_t k = stop - 1;
+      const uint32_t fix = fixes(k) | (delayed(k) & kDelayedArrive);
+      if (fix) p.launches.push_back({FIX, k, 1, 0, 0, fix});
+      if (delayed(k) & kDelayedLatch) p.launches.push_back({LATCH, k, 1, 0, 0, kDelayedLatch});
+      if (record(k)) p.launches.push_back({RECORD, k, 1, 0, 0, 0});
     }
     e = stop;
   }
   return p;
+}
+
+// uwvk_pose_run_log_fixes' argument check over epochs [first, first + count):
+// every flagged kind has its index and payload arrays and a row inside them
+// (an out-of-range row would be an out-of-bounds device read).  Reads the host
+// arrays only; the device pointers are tested for null.
+inline bool fixes_valid(const uwvk_pose_fixes* fx, int64_t first, int64_t count) {
+  if (!fx->host_flags) return false;
+  struct K {
+    uint32_t bit;
+    const int32_t* index;
+    const double* rows;
+    int64_t n;
+  } ks[3] = {{UWVK_FIX_XY, fx->xy_index, fx->xy, fx->n_xy},
+             {UWVK_FIX_Z, fx->z_index, fx->z, fx->n_z},
+             {UWVK_FIX_GEO, fx->geo_index, fx->geo, fx->n_geo}};
+  for (int64_t e = first; e < first + count; e++) {
+    const uint32_t f = fx->host_flags[e];
+    if (f & ~(UWVK_FIX_XY | UWVK_FIX_Z | UWVK_FIX_GEO)) return false;
+    for (const K& k : ks)
+      if ((f & k.bit) && (!k.index || !k.rows || k.index[e] < 0 || k.index[e] >= k.n)) return false;
+  }
+  return true;
+}
+
+// uwvk_pose_run_log_delayed's argument check (epochs: the log's), and what
+// [first, first + count) holds of the rows (out): plan_run's delayed flags and
+// the latches to run.  An out-of-range row would be an out-of-bounds device
+// access.  Reads the host arrays only, like fixes_valid.
+struct DelayedEvents {
+  std::vector<uint32_t> flags;                       // kDelayedArrive / kDelayedLatch of epoch first + k
+  std::vector<std::pair<int64_t, int32_t>> latches;  // (latch epoch, row) of the range, ascending
+};
+inline bool delayed_events(const uwvk_pose_delayed* d, int64_t epochs, int64_t first, int64_t count,
+                           DelayedEvents* out) {
+  if (d->n < 0) return false;
+  if (d->n > 0 && (!d->index || !d->latch_epoch || !d->xy || !d->latched)) return false;
+  out->flags.assign((size_t)count, 0u);
+  out->latches.clear();
+  for (int64_t r = 0; r < d->n; r++) {
+    const int64_t L = d->latch_epoch[r];
+    if (L < -1 || L >= epochs) return false;
+    if (L >= first && L < first + count) {
+      out->flags[(size_t)(L - first)] |= kDelayedLatch;
+      out->latches.emplace_back(L, (int32_t)r);
+    }
+  }
+  std::sort(out->latches.begin(), out->latches.end());
+  if (!d->index) return true;  // n == 0, no index array: no events
+  for (int64_t e = first; e < first + count; e++) {
+    const int64_t r = d->index[e];
+    if (r < -1 || r >= d->n) return false;
+    if (r < 0) continue;
+    if (d->latch_epoch[r] >= e) return false;
+    out->flags[(size_t)(e - first)] |= kDelayedArrive;
+  }
+  return true;
 }
 
 // Last-generation spreading.  Blocks of one XCD are dispatched in order to

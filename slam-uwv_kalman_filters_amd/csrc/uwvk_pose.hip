@@ -1,8 +1,10 @@
 // uwvk_pose.hip — the uwvk_pose_* C ABI: the handle, its buffers, the copies
 // and the launches.  No kernels here: they are instantiated in the
 // uwvk_pose_k_*.hip and uwvk_psp_*.hip translation units (launchers in
-// uwvk_pose_kernels.hpp / uwvk_psp.hpp), and what uwvk_pose_run_log launches is
-// decided by the pure host planner in uwvk_plan.hpp.
+// uwvk_pose_kernels.hpp / uwvk_psp.hpp).  What a uwvk_pose_run_log* call
+// launches, and in which order, is one list made by the pure host planner
+// (plan_run, uwvk_plan.hpp); run_log checks the arguments, walks that list and
+// has one case per launch kind.
 #include "uwvk_pose_kernels.hpp"
 #include "uwvk_psp.hpp"
 #include "uwvk_plan.hpp"
@@ -602,174 +604,135 @@ static StatTruth stat_truth(const uwvk_pose* h, const double* truth) {
 // the ensemble partials' area, after the rotation-rate area: d_scratch + 256 + 3 batch
 static double* stats_partials(const uwvk_pose* h) { return h->d_scratch + 256 + 3 * h->batch; }
 
-// The launches of epochs [first, first + count), queued on the handle's stream.
-// ea: the log's arguments (a copy per call: the launch fields start cleared);
-// hf: the host flags of these epochs (PSP path); sh: the handle's PoseShared
-// after upload_shared.
-// fx: the position fixes of uwvk_pose_run_log_fixes (validated over the call's
-// range by fixes_valid), or null.
-// dl: the delayed XY rows of uwvk_pose_run_log_delayed over the call's range
-// (delayed_plan), or null.
-struct DelayedRun {
-  const uwvk_pose_delayed* d;
-  int64_t first;                                     // flags[k] is epoch first + k
-  std::vector<uint32_t> flags;                       // kDelayedArrive / kDelayedLatch per epoch of the call
-  std::vector<std::pair<int64_t, int32_t>> latches;  // (latch epoch, row) of the call's range, ascending
-};
 static_assert(kFixDelayed == kDelayedArrive, "FixArgs::kinds holds the planner's arrival bit");
 
-// the latches of epoch e: the state's XY position into every row with L[r] = e
-static hipError_t latch_epoch_rows(uwvk_pose* h, const DelayedRun& dl, int64_t e) {
-  auto it = std::lower_bound(dl.latches.begin(), dl.latches.end(), std::make_pair(e, (int32_t)-1));
+// LATCH: the state's XY position into every row r of `latched` with latch_epoch[r] = e
+static hipError_t latch_epoch_rows(uwvk_pose* h, const DelayedEvents& ev, double* latched, int64_t e) {
+  auto it = std::lower_bound(ev.latches.begin(), ev.latches.end(), std::make_pair(e, (int32_t)-1));
   LatchRows rows{};
   hipError_t le = hipSuccess;
-  for (; le == hipSuccess && it != dl.latches.end() && it->first == e; ++it) {
+  for (; le == hipSuccess && it != ev.latches.end() && it->first == e; ++it) {
     rows.row[rows.n++] = it->second;
     if (rows.n == kLatchRows) {
-      le = launch_pose_latch(h->dof, h->stream, h->d_mu, h->batch, dl.d->latched, rows);
+      le = launch_pose_latch(h->dof, h->stream, h->d_mu, h->batch, latched, rows);
       rows.n = 0;
     }
   }
-  if (le == hipSuccess && rows.n > 0) le = launch_pose_latch(h->dof, h->stream, h->d_mu, h->batch, dl.d->latched, rows);
+  if (le == hipSuccess && rows.n > 0) le = launch_pose_latch(h->dof, h->stream, h->d_mu, h->batch, latched, rows);
   return le;
 }
 
-static uwvk_status run_epochs(uwvk_pose* h, const PoseBufs& b, const PoseShared& sh, EpochArgs ea, const uint32_t* hf,
-                              int64_t first, int64_t count, const uwvk_pose_fixes* fx, const DelayedRun* dl) {
+// FIX on PSP: epoch e's position fixes and its arriving delayed row in one launch (kinds: Launch::ev_any)
+static hipError_t fix_psp(uwvk_pose* h, const PoseBufs& b, const PoseShared& sh, const uwvk_pose_fixes* fx,
+                          const uwvk_pose_delayed* d, int64_t e, uint32_t kinds) {
   const int64_t B = h->batch;
-  if (use_dense(h)) {  // literal kernels: one fused launch per epoch
-    for (int64_t e = first; e < first + count; e++) {
-      ea.first = e;
-      ea.count = 1;
-      HIPCHK(launch_pose_epoch(h->dof, h->stream, b, sh, ea));
-      const uint32_t kinds = fx ? fx->host_flags[e] : 0u;
-      const uint32_t dk = dl ? dl->flags[(size_t)(e - dl->first)] : 0u;
-      if (!kinds && !dk) continue;
-      // the epoch's fixes: the literal k_pose_update per kind, on the log's device rows
-      auto fix = [&](int kind, int slot, int m, const double* row, const double* cov, const double* v3) {
-        MeasArgs ma{};
-        ma.mu = row;
-        std::memcpy(ma.shared_cov, cov, (size_t)m * m * 8);
-        if (v3)
-          for (int k = 0; k < 3; k++) ma.v3[k] = v3[k];
-        ma.accepted = fx->accept_counts ? h->d_accepted : nullptr;
-        hipError_t le = launch_pose_update(h->dof, kind, h->stream, b, sh, ma, m);
-        if (le == hipSuccess && fx->accept_counts)
-          le = launch_fix_count(h->stream, h->d_accepted, B, slot, fx->accept_counts);
-        return le;
-      };
-      if (kinds & UWVK_FIX_XY) HIPCHK(fix(MK_XY, 0, 2, fx->xy + (int64_t)fx->xy_index[e] * B * 2, fx->xy_cov, nullptr));
-      if (kinds & UWVK_FIX_Z) HIPCHK(fix(MK_Z, 1, 1, fx->z + (int64_t)fx->z_index[e] * B, &fx->z_cov, nullptr));
-      if (kinds & UWVK_FIX_GEO)
-        HIPCHK(fix(MK_GEO, 2, 2, fx->geo + (int64_t)fx->geo_index[e] * B * 2, fx->geo_cov, fx->gps_in_body));
-      if (dk & kDelayedArrive) {
-        // the arriving delayed row: k_pose_update on its device rows, delayed_xy the latched row
-        const uwvk_pose_delayed* d = dl->d;
-        const int64_t off = (int64_t)d->index[e] * B * 2;
-        MeasArgs ma{};
-        ma.mu = d->xy + off;
-        std::memcpy(ma.shared_cov, d->xy_cov, sizeof(d->xy_cov));
-        ma.extra = d->latched + off;
-        ma.check_extra = 1;
-        ma.accepted = d->accept_counts ? h->d_accepted : nullptr;
-        HIPCHK(launch_pose_update(h->dof, MK_DELAYED, h->stream, b, sh, ma, 2));
-        if (d->accept_counts) HIPCHK(launch_delayed_count(h->stream, h->d_accepted, B, d->accept_counts));
-      }
-      if (dk & kDelayedLatch) HIPCHK(latch_epoch_rows(h, *dl, e));
-    }
-    return UWVK_OK;
+  FixArgs fa{};
+  fa.kinds = kinds;
+  if (kinds & kFixDelayed) {
+    const int64_t off = (int64_t)d->index[e] * B * 2;
+    fa.dxy = d->xy + off;
+    fa.latched = d->latched + off;
+    std::memcpy(fa.dxy_cov, d->xy_cov, sizeof(fa.dxy_cov));
+    fa.delayed_counts = d->accept_counts;
   }
-  // PSP: the launches of plan_delayed_epochs (uwvk_plan.hpp; plan_fix_epochs' without delayed rows,
-  // plan_epochs' without fixes either), in order
-  const EpochPlan plan = plan_delayed_epochs(hf, fx ? fx->host_flags + first : nullptr,
-                                             dl ? dl->flags.data() + (first - dl->first) : nullptr, first, count,
-                                             facts(h));
-  for (const Launch& l : plan.launches) {
-    ea.first = l.first;
-    ea.count = l.count;
-    if (l.kind == LATCH) {
-      HIPCHK(latch_epoch_rows(h, *dl, l.first));
-      continue;
-    }
-    if (l.kind == FIX) {
-      // the epoch's position fixes (and its arriving delayed row) in one launch; they leave pdec as it is
-      const int64_t e = l.first;
-      FixArgs fa{};
-      fa.kinds = l.ev_any;
-      if (fa.kinds & kFixDelayed) {
-        const uwvk_pose_delayed* d = dl->d;
-        const int64_t off = (int64_t)d->index[e] * B * 2;
-        fa.dxy = d->xy + off;
-        fa.latched = d->latched + off;
-        std::memcpy(fa.dxy_cov, d->xy_cov, sizeof(fa.dxy_cov));
-        fa.delayed_counts = d->accept_counts;
-      }
-      if (fa.kinds & (UWVK_FIX_XY | UWVK_FIX_Z | UWVK_FIX_GEO)) {  // (an arrival alone: fx may be null)
-        if (fa.kinds & UWVK_FIX_XY) fa.xy = fx->xy + (int64_t)fx->xy_index[e] * B * 2;
-        if (fa.kinds & UWVK_FIX_Z) fa.z = fx->z + (int64_t)fx->z_index[e] * B;
-        if (fa.kinds & UWVK_FIX_GEO) fa.geo = fx->geo + (int64_t)fx->geo_index[e] * B * 2;
-        std::memcpy(fa.xy_cov, fx->xy_cov, sizeof(fa.xy_cov));
-        fa.z_cov = fx->z_cov;
-        std::memcpy(fa.geo_cov, fx->geo_cov, sizeof(fa.geo_cov));
-        std::memcpy(fa.gps_in_body, fx->gps_in_body, sizeof(fa.gps_in_body));
-        fa.accept_counts = fx->accept_counts;
-      }
-      HIPCHK(launch_psp_fix(h->dof, h->stream, b, sh, fa));
-      continue;
-    }
-    if (l.kind == EFFORTS) {
-      // constrainVelocity (PEffVO) or the full measurementEfforts (psp_update_eff)
-      if (!l.vo) h->pdec = false;  // the full model couples the parameters (PD off from here)
-      HIPCHK(launch_psp_efforts(h->dof, l.vo, h->stream, b, sh, ea));
-      continue;
-    }
-    const bool pair = l.kind == EPOCH_PAIR;
-    // the pair kernel runs a 53-DOF state decoupled only (runs_pair implies runs_pd there)
-    if (pair && h->dof == 53 && !l.pd) return UWVK_EINVAL;
-    // the persistent, ticket-ordered launch: the pair kernel's only form, the
-    // default, and the static launch's stand-in where block placement is not
-    // the round-robin its XCD-ordered tail needs (a partitioned device, another
-    // runtime): tickets spread the tail without any placement assumption
-    const bool spread = static_may_spread(h->batch, h->tail_slots, h->lds_pad);
-    Geometry g;
-    ea.ticket = nullptr;
-    if (pair || h->persist || (spread && !xcd_round_robin(h->device))) {
-      const int64_t slots = pair ? psp_pair_slots(h->device) : psp_epoch_slots(h->dof, h->device, true, l.pd);
-      HIPCHK(slots > 0 ? hipSuccess : hipErrorInvalidValue);
-      g = persist_geometry(pair ? h->batch / 2 : h->batch, slots, h->tail_slots, h->tail_force, h->lds_pad, l.count,
-                           pair, h->wait_bound);
-      // ticket_next advances only once the launch is queued: a launch that
-      // fails leaves the device counter where it was
-      ea.ticket = h->d_ticket;
-      ea.ticket_base = h->ticket_next;
-    } else {
-      const int64_t slots = spread && h->tail_slots <= 0 ? psp_epoch_slots_per_xcd(h->dof, h->device, l.pd) : 0;
-      g = static_geometry(h->batch, slots, h->tail_slots, h->tail_force, h->lds_pad, l.count, h->wait_bound);
-    }
-    if (g.tail_need > 0) {
-      HIPCHK(tail_buffers(h, g.tail_need, g.tail_cap));
-      ea.tail_flag = h->d_tail_flag;
-      ea.tail_carry = h->d_tail_carry;
-      ea.tag = h->tail_tag;
-    }
-    ea.chunks = g.chunks; ea.n_x = g.n_x; ea.tail0 = g.tail0; ea.r_x = g.r_x;
-    ea.units = g.units; ea.wait_bound = g.wait_bound;
-    PoseBufs bl = b;
-    if (l.pd) bl.Qp = h->d_Qp_pd;
-    const hipError_t le = pair ? launch_psp_epoch_pair(h->stream, bl, sh, ea, g.grid, l.ev_any, l.pd)
-                               : launch_psp_epoch(h->dof, h->stream, bl, sh, ea, g.grid, l.ev_any, h->lds_pad, l.pd);
-    if (le != hipSuccess) {
-      ::uwvk::note_hip_error((int)le, pair ? "launch_psp_epoch_pair" : "launch_psp_epoch");
-      // a persistent launch that did not run took no tickets: restart the
-      // counter from zero (stream-ordered, before any later launch)
-      if (ea.ticket) {
-        h->ticket_next = 0;
-        (void)hipMemsetAsync(h->d_ticket, 0, 4, h->stream);
-      }
-      return UWVK_EDEVICE;
-    }
-    if (ea.ticket) h->ticket_next += ea.units;  // the tickets the launch takes
+  if (kinds & (UWVK_FIX_XY | UWVK_FIX_Z | UWVK_FIX_GEO)) {  // (an arrival alone: fx may be null)
+    if (kinds & UWVK_FIX_XY) fa.xy = fx->xy + (int64_t)fx->xy_index[e] * B * 2;
+    if (kinds & UWVK_FIX_Z) fa.z = fx->z + (int64_t)fx->z_index[e] * B;
+    if (kinds & UWVK_FIX_GEO) fa.geo = fx->geo + (int64_t)fx->geo_index[e] * B * 2;
+    std::memcpy(fa.xy_cov, fx->xy_cov, sizeof(fa.xy_cov));
+    fa.z_cov = fx->z_cov;
+    std::memcpy(fa.geo_cov, fx->geo_cov, sizeof(fa.geo_cov));
+    std::memcpy(fa.gps_in_body, fx->gps_in_body, sizeof(fa.gps_in_body));
+    fa.accept_counts = fx->accept_counts;
   }
+  return launch_psp_fix(h->dof, h->stream, b, sh, fa);
+}
+
+// FIX on a dense handle: the literal k_pose_update per kind on the log's device
+// rows, in the order XY, Z, Geographic, delayed (delayed_xy the latched row),
+// each followed by its count kernel
+static hipError_t fix_dense(uwvk_pose* h, const PoseBufs& b, const PoseShared& sh, const uwvk_pose_fixes* fx,
+                            const uwvk_pose_delayed* d, int64_t e, uint32_t kinds) {
+  const int64_t B = h->batch;
+  auto fix = [&](int kind, int slot, int m, const double* row, const double* cov, const double* v3) {
+    MeasArgs ma{};
+    ma.mu = row;
+    std::memcpy(ma.shared_cov, cov, (size_t)m * m * 8);
+    if (v3)
+      for (int k = 0; k < 3; k++) ma.v3[k] = v3[k];
+    ma.accepted = fx->accept_counts ? h->d_accepted : nullptr;
+    hipError_t le = launch_pose_update(h->dof, kind, h->stream, b, sh, ma, m);
+    if (le == hipSuccess && fx->accept_counts) le = launch_fix_count(h->stream, h->d_accepted, B, slot, fx->accept_counts);
+    return le;
+  };
+  hipError_t le = hipSuccess;
+  if (kinds & UWVK_FIX_XY) le = fix(MK_XY, 0, 2, fx->xy + (int64_t)fx->xy_index[e] * B * 2, fx->xy_cov, nullptr);
+  if (le == hipSuccess && (kinds & UWVK_FIX_Z)) le = fix(MK_Z, 1, 1, fx->z + (int64_t)fx->z_index[e] * B, &fx->z_cov, nullptr);
+  if (le == hipSuccess && (kinds & UWVK_FIX_GEO))
+    le = fix(MK_GEO, 2, 2, fx->geo + (int64_t)fx->geo_index[e] * B * 2, fx->geo_cov, fx->gps_in_body);
+  if (le == hipSuccess && (kinds & kFixDelayed)) {
+    const int64_t off = (int64_t)d->index[e] * B * 2;
+    MeasArgs ma{};
+    ma.mu = d->xy + off;
+    std::memcpy(ma.shared_cov, d->xy_cov, sizeof(d->xy_cov));
+    ma.extra = d->latched + off;
+    ma.check_extra = 1;
+    ma.accepted = d->accept_counts ? h->d_accepted : nullptr;
+    le = launch_pose_update(h->dof, MK_DELAYED, h->stream, b, sh, ma, 2);
+    if (le == hipSuccess && d->accept_counts) le = launch_delayed_count(h->stream, h->d_accepted, B, d->accept_counts);
+  }
+  return le;
+}
+
+// EPOCH_ONE / EPOCH_PAIR: the PSP epoch kernel over l's epochs.  ea: the log's
+// arguments with first and count set; the launch's geometry is filled in here
+static uwvk_status launch_epochs(uwvk_pose* h, const PoseBufs& b, const PoseShared& sh, EpochArgs ea, const Launch& l) {
+  const bool pair = l.kind == EPOCH_PAIR;
+  // the pair kernel runs a 53-DOF state decoupled only (runs_pair implies runs_pd there)
+  if (pair && h->dof == 53 && !l.pd) return UWVK_EINVAL;
+  // the persistent, ticket-ordered launch: the pair kernel's only form, the
+  // default, and the static launch's stand-in where block placement is not
+  // the round-robin its XCD-ordered tail needs (a partitioned device, another
+  // runtime): tickets spread the tail without any placement assumption
+  const bool spread = static_may_spread(h->batch, h->tail_slots, h->lds_pad);
+  Geometry g;
+  ea.ticket = nullptr;
+  if (pair || h->persist || (spread && !xcd_round_robin(h->device))) {
+    const int64_t slots = pair ? psp_pair_slots(h->device) : psp_epoch_slots(h->dof, h->device, true, l.pd);
+    HIPCHK(slots > 0 ? hipSuccess : hipErrorInvalidValue);
+    g = persist_geometry(pair ? h->batch / 2 : h->batch, slots, h->tail_slots, h->tail_force, h->lds_pad, l.count,
+                         pair, h->wait_bound);
+    // ticket_next advances only once the launch is queued: a launch that
+    // fails leaves the device counter where it was
+    ea.ticket = h->d_ticket;
+    ea.ticket_base = h->ticket_next;
+  } else {
+    const int64_t slots = spread && h->tail_slots <= 0 ? psp_epoch_slots_per_xcd(h->dof, h->device, l.pd) : 0;
+    g = static_geometry(h->batch, slots, h->tail_slots, h->tail_force, h->lds_pad, l.count, h->wait_bound);
+  }
+  if (g.tail_need > 0) {
+    HIPCHK(tail_buffers(h, g.tail_need, g.tail_cap));
+    ea.tail_flag = h->d_tail_flag;
+    ea.tail_carry = h->d_tail_carry;
+    ea.tag = h->tail_tag;
+  }
+  ea.chunks = g.chunks; ea.n_x = g.n_x; ea.tail0 = g.tail0; ea.r_x = g.r_x;
+  ea.units = g.units; ea.wait_bound = g.wait_bound;
+  PoseBufs bl = b;
+  if (l.pd) bl.Qp = h->d_Qp_pd;
+  const hipError_t le = pair ? launch_psp_epoch_pair(h->stream, bl, sh, ea, g.grid, l.ev_any, l.pd)
+                             : launch_psp_epoch(h->dof, h->stream, bl, sh, ea, g.grid, l.ev_any, h->lds_pad, l.pd);
+  if (le != hipSuccess) {
+    ::uwvk::note_hip_error((int)le, pair ? "launch_psp_epoch_pair" : "launch_psp_epoch");
+    // a persistent launch that did not run took no tickets: restart the
+    // counter from zero (stream-ordered, before any later launch)
+    if (ea.ticket) {
+      h->ticket_next = 0;
+      (void)hipMemsetAsync(h->d_ticket, 0, 4, h->stream);
+    }
+    return UWVK_EDEVICE;
+  }
+  if (ea.ticket) h->ticket_next += ea.units;  // the tickets the launch takes
   return UWVK_OK;
 }
 
@@ -777,65 +740,10 @@ int64_t uwvk_pose_track_records(int64_t first, int64_t count, int64_t every) {
   return first < 0 || count < 0 || every <= 0 ? 0 : track_records(first, count, every);
 }
 
-// uwvk_pose_run_log (track == null: the whole range is one segment) and
-// uwvk_pose_run_log_track (the range cut after every record epoch,
-// track_segments; after a segment that ends in one, the snapshot of the state
-// its last launch stored, and the statistics, into record r's slots)
-// uwvk_pose_run_log_fixes' argument check over epochs [first, first + count):
-// every flagged kind has its index and payload arrays and a row inside them
-// (an out-of-range row would be an out-of-bounds device read)
-static bool fixes_valid(const uwvk_pose_fixes* fx, int64_t first, int64_t count) {
-  if (!fx->host_flags) return false;
-  struct K {
-    uint32_t bit;
-    const int32_t* index;
-    const double* rows;
-    int64_t n;
-  } ks[3] = {{UWVK_FIX_XY, fx->xy_index, fx->xy, fx->n_xy},
-             {UWVK_FIX_Z, fx->z_index, fx->z, fx->n_z},
-             {UWVK_FIX_GEO, fx->geo_index, fx->geo, fx->n_geo}};
-  for (int64_t e = first; e < first + count; e++) {
-    const uint32_t f = fx->host_flags[e];
-    if (f & ~(UWVK_FIX_XY | UWVK_FIX_Z | UWVK_FIX_GEO)) return false;
-    for (const K& k : ks)
-      if ((f & k.bit) && (!k.index || !k.rows || k.index[e] < 0 || k.index[e] >= k.n)) return false;
-  }
-  return true;
-}
-
-// uwvk_pose_run_log_fixes: fx non-null adds the position fixes (a fix epoch ends
-// a launch, plan_fix_epochs; the track's snapshot of that epoch follows its FIX launch)
-// uwvk_pose_run_log_delayed's argument check, and the per-epoch delayed flags
-// and latch list of [first, first + count) (out).  An out-of-range row would be
-// an out-of-bounds device access.
-static bool delayed_plan(const uwvk_pose_delayed* d, int64_t epochs, int64_t first, int64_t count, DelayedRun* out) {
-  if (d->n < 0) return false;
-  if (d->n > 0 && (!d->index || !d->latch_epoch || !d->xy || !d->latched)) return false;
-  out->d = d;
-  out->first = first;
-  out->flags.assign((size_t)count, 0u);
-  for (int64_t r = 0; r < d->n; r++) {
-    const int64_t L = d->latch_epoch[r];
-    if (L < -1 || L >= epochs) return false;
-    if (L >= first && L < first + count) {
-      out->flags[(size_t)(L - first)] |= kDelayedLatch;
-      out->latches.emplace_back(L, (int32_t)r);
-    }
-  }
-  std::sort(out->latches.begin(), out->latches.end());
-  if (!d->index) return true;  // n == 0, no index array: no events
-  for (int64_t e = first; e < first + count; e++) {
-    const int64_t r = d->index[e];
-    if (r < -1 || r >= d->n) return false;
-    if (r < 0) continue;
-    if (d->latch_epoch[r] >= e) return false;
-    out->flags[(size_t)(e - first)] |= kDelayedArrive;
-  }
-  return true;
-}
-
-// uwvk_pose_run_log_delayed: dly non-null adds the delayed XY rows (an arrival
-// and a latch end a launch, plan_delayed_epochs)
+// The four uwvk_pose_run_log* entry points: track, fx and dly are each null or
+// that call's argument.  After the argument checks (fixes_valid and
+// delayed_events, uwvk_plan.hpp) the whole call is planned once by plan_run
+// and its launches are queued on the handle's stream in the plan's order.
 static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
                            uint32_t* accept_counts, const uwvk_pose_track* track,
                            const uwvk_pose_fixes* fx = nullptr, const uwvk_pose_delayed* dly = nullptr) {
@@ -844,9 +752,8 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
                 track->capacity < track_records(first, count, track->every)))
     return UWVK_EINVAL;
   if (fx && !fixes_valid(fx, first, count)) return UWVK_EINVAL;
-  DelayedRun drun{};
-  if (dly && !delayed_plan(dly, log->epochs, first, count, &drun)) return UWVK_EINVAL;
-  const DelayedRun* dl = dly ? &drun : nullptr;
+  DelayedEvents events;
+  if (dly && !delayed_events(dly, log->epochs, first, count, &events)) return UWVK_EINVAL;
   if (!h->has_state) return UWVK_ENOTINIT;
   // ABI 3: a hand-off timeout of an earlier, completed launch is reported here
   // (or by uwvk_pose_synchronize), before any new work is queued
@@ -885,21 +792,45 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
     ea.efforts_only = 0;
   }
   const PoseShared sh = h->sh;  // after upload_shared (it refreshes the Q shape)
-  if (!track) return run_epochs(h, b, sh, ea, hf, first, count, fx, dl);
+  const EpochPlan plan = plan_run(hf, fx ? fx->host_flags + first : nullptr, dly ? events.flags.data() : nullptr,
+                                  track ? track->every : 0, first, count, facts(h));
   const int s = h->store, nout = 3 * s + 2;
   int64_t r = 0;  // the next record of this call
-  for (const TrackSegment& seg : track_segments(first, count, track->every)) {
-    const uwvk_status st = run_epochs(h, b, sh, ea, hf ? hf + (seg.first - first) : nullptr, seg.first, seg.count, fx, dl);
-    if (st != UWVK_OK) return st;
-    if (!seg.record) continue;
-    if (track->mean || track->variance)
-      HIPCHK(launch_pose_track(h->dof, h->stream, h->d_mu, h->d_sigma, h->batch,
-                               track->mean ? track->mean + r * h->batch * s : nullptr,
-                               track->variance ? track->variance + r * h->batch * h->dof : nullptr));
-    if (track->stats)
-      HIPCHK(launch_pose_stats(h->dof, h->stream, b, stat_truth(h, track->truth ? track->truth + r * s : nullptr),
-                               track->stats + r * nout, stats_partials(h)));
-    r++;
+  for (const Launch& l : plan.launches) {
+    ea.first = l.first;
+    ea.count = l.count;
+    switch (l.kind) {
+      case EPOCH_ONE:
+      case EPOCH_PAIR: {
+        const uwvk_status st = launch_epochs(h, b, sh, ea, l);
+        if (st != UWVK_OK) return st;
+        break;
+      }
+      case EPOCH_DENSE:  // the literal kernels: the epoch's predict and log updates fused
+        HIPCHK(launch_pose_epoch(h->dof, h->stream, b, sh, ea));
+        break;
+      case EFFORTS:
+        // constrainVelocity (PEffVO) or the full measurementEfforts (psp_update_eff)
+        if (!l.vo) h->pdec = false;  // the full model couples the parameters (PD off from here)
+        HIPCHK(launch_psp_efforts(h->dof, l.vo, h->stream, b, sh, ea));
+        break;
+      case FIX:  // the position updates leave pdec as it is
+        HIPCHK(use_dense(h) ? fix_dense(h, b, sh, fx, dly, l.first, l.ev_any) : fix_psp(h, b, sh, fx, dly, l.first, l.ev_any));
+        break;
+      case LATCH:
+        HIPCHK(latch_epoch_rows(h, events, dly->latched, l.first));
+        break;
+      case RECORD:  // the snapshot of the state the epoch's last launch stored, and the statistics, into slot r
+        if (track->mean || track->variance)
+          HIPCHK(launch_pose_track(h->dof, h->stream, h->d_mu, h->d_sigma, h->batch,
+                                   track->mean ? track->mean + r * h->batch * s : nullptr,
+                                   track->variance ? track->variance + r * h->batch * h->dof : nullptr));
+        if (track->stats)
+          HIPCHK(launch_pose_stats(h->dof, h->stream, b, stat_truth(h, track->truth ? track->truth + r * s : nullptr),
+                                   track->stats + r * nout, stats_partials(h)));
+        r++;
+        break;
+    }
   }
   return UWVK_OK;
 }

@@ -1,75 +1,18 @@
 // delayed_plan_test.cpp — the launch plan of uwvk_pose_run_log_delayed
-// (plan_delayed_epochs, csrc/uwvk_plan.hpp) on the CPU: without delayed flags
-// it is plan_fix_epochs' plan; an arrival or a latch ends a launch; the epoch's
-// FIX launch (fixes and the arrival, one launch) comes after its EFFORTS launch
-// and before its LATCH launch; pdec is carried from piece to piece; and a
-// per-epoch restatement of the rule over seeded random flag sets.
-// Exit 0 = all checks hold.
-#include <cstdio>
+// (plan_run with delayed flags, csrc/uwvk_plan.hpp) on the CPU: without delayed
+// or fix flags it is plan_epochs' plan; an arrival or a latch ends a launch; the
+// epoch's FIX launch (fixes and the arrival, one launch) comes after its EFFORTS
+// launch and before its LATCH launch, a track record last; pdec is carried from
+// piece to piece; a per-epoch restatement of the rule over seeded random flag
+// sets and track strides; the plan of a dense handle; and the argument check
+// delayed_events.  Exit 0 = all checks hold.
 #include <random>
-#include <string>
 
-#include "../../slam-uwv_kalman_filters_amd/csrc/uwvk_plan.hpp"
-
-using namespace uwvk;
-
-static int g_fail = 0;
-#define CHECK(c)                                               \
-  do {                                                         \
-    if (!(c)) {                                                \
-      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                \
-    }                                                          \
-  } while (0)
-
-constexpr uint32_t IMU = UWVK_EV_ACC, P = UWVK_EV_PRESSURE, A = UWVK_EV_ADCP, E = UWVK_EV_EFFORTS,
-                   VO = UWVK_EV_EFFORTS_VELOCITY_ONLY;
-constexpr uint32_t XY = UWVK_FIX_XY, Z = UWVK_FIX_Z, GEO = UWVK_FIX_GEO;
-constexpr uint32_t ARR = kDelayedArrive, LAT = kDelayedLatch;
-
-// dof 53, an even batch, every option at its default, a decoupled state and a
-// simple, parameter-diagonal Q (plan_test.cpp's defaults)
-static EpochFacts defaults() { return {53, 64, 1, 1, 1, 0, false, true, true, true}; }
-
-// "PAIR[0,60)pd EFFORTS(59,vo=0) FIX(59,m=9) LATCH(59) ONE[60,120) pdec=0"
-static std::string show(const EpochPlan& p) {
-  std::string s;
-  for (const Launch& l : p.launches) {
-    if (l.kind == EFFORTS) s += "EFFORTS(" + std::to_string(l.first) + ",vo=" + std::to_string(l.vo) + ") ";
-    else if (l.kind == FIX) s += "FIX(" + std::to_string(l.first) + ",m=" + std::to_string(l.ev_any) + ") ";
-    else if (l.kind == LATCH) s += "LATCH(" + std::to_string(l.first) + ") ";
-    else
-      s += std::string(l.kind == EPOCH_PAIR ? "PAIR[" : "ONE[") + std::to_string(l.first) + "," +
-           std::to_string(l.first + l.count) + ")" + (l.pd ? "pd " : " ");
-  }
-  return s + "pdec=" + std::to_string((int)p.pdec);
-}
-
-using Ev = std::initializer_list<std::pair<int64_t, uint32_t>>;
-static std::vector<uint32_t> flags(int64_t n, uint32_t base, Ev ev = {}) {
-  std::vector<uint32_t> f((size_t)n, base);
-  for (auto& e : ev) f[(size_t)e.first] |= e.second;
-  return f;
-}
-
-static bool same(const EpochPlan& a, const EpochPlan& b) {
-  if (a.pdec != b.pdec || a.launches.size() != b.launches.size()) return false;
-  for (size_t i = 0; i < a.launches.size(); i++) {
-    const Launch &x = a.launches[i], &y = b.launches[i];
-    if (x.kind != y.kind || x.first != y.first || x.count != y.count || x.pd != y.pd || x.vo != y.vo ||
-        x.ev_any != y.ev_any)
-      return false;
-  }
-  return true;
-}
+#include "plan_check.hpp"
 
 static void expect(const std::vector<uint32_t>& f, const std::vector<uint32_t>& fx, const std::vector<uint32_t>& dl,
                    const EpochFacts& facts, const char* want, int line) {
-  const std::string got = show(plan_delayed_epochs(f.data(), fx.data(), dl.data(), 0, (int64_t)f.size(), facts));
-  if (got != want) {
-    std::printf("FAIL line %d:\n  got  %s\n  want %s\n", line, got.c_str(), want);
-    g_fail++;
-  }
+  expect_plan(plan_run(f.data(), fx.data(), dl.data(), 0, 0, (int64_t)f.size(), facts), want, line);
 }
 #define EXPECT(f, fx, dl, facts, want) expect(f, fx, dl, facts, want, __LINE__)
 
@@ -118,43 +61,46 @@ static void test_cases() {
     const auto dl = flags(100, 0, {{48, LAT}, {60, ARR}});
     const auto fx = flags(100, 0, {{60, GEO}});
     const auto fl = flags(100, IMU);
-    CHECK(show(plan_delayed_epochs(fl.data(), fx.data(), dl.data(), 1000, 100, d)) ==
+    CHECK(show(plan_run(fl.data(), fx.data(), dl.data(), 0, 1000, 100, d)) ==
           "PAIR[1000,1049)pd LATCH(1048) PAIR[1049,1061)pd FIX(1060,m=12) PAIR[1061,1100)pd pdec=1");
-    CHECK(show(plan_delayed_epochs(fl.data(), nullptr, dl.data(), 1000, 100, d)) ==
+    CHECK(show(plan_run(fl.data(), nullptr, dl.data(), 0, 1000, 100, d)) ==
           "PAIR[1000,1049)pd LATCH(1048) PAIR[1049,1061)pd FIX(1060,m=8) PAIR[1061,1100)pd pdec=1");
-    CHECK(same(plan_delayed_epochs(fl.data(), fx.data(), nullptr, 1000, 100, d),
-               plan_fix_epochs(fl.data(), fx.data(), 1000, 100, d)));
-    CHECK(same(plan_delayed_epochs(fl.data(), nullptr, nullptr, 1000, 100, d), plan_epochs(fl.data(), 1000, 100, d)));
-    CHECK(show(plan_delayed_epochs(nullptr, nullptr, nullptr, 7, 0, d)) == "pdec=1");
+    CHECK(show(plan_run(fl.data(), fx.data(), nullptr, 0, 1000, 100, d)) ==
+          "PAIR[1000,1061)pd FIX(1060,m=4) PAIR[1061,1100)pd pdec=1");
+    CHECK(same(plan_run(fl.data(), nullptr, nullptr, 0, 1000, 100, d), plan_epochs(fl.data(), 1000, 100, d)));
+    CHECK(show(plan_run(nullptr, nullptr, nullptr, 0, 7, 0, d)) == "pdec=1");
     EpochFacts g = d;
     g.pdec = false;
-    CHECK(show(plan_delayed_epochs(nullptr, nullptr, nullptr, 7, 0, g)) == "pdec=0");
+    CHECK(show(plan_run(nullptr, nullptr, nullptr, 0, 7, 0, g)) == "pdec=0");
   }
   // calls over adjacent ranges concatenate (a row latched in one, arriving in the next)
   {
     const auto fl = flags(120, IMU, {{59, E | VO}});
     const auto fx = flags(120, 0, {{59, XY}});
     const auto dl = flags(120, 0, {{58, LAT}, {60, ARR}, {89, LAT}});
-    auto part = [&](int64_t a, int64_t n) {
-      const std::string t = show(plan_delayed_epochs(fl.data() + a, fx.data() + a, dl.data() + a, a, n, d));
-      return t.substr(0, t.rfind("pdec="));
-    };
-    CHECK(part(0, 60) + part(60, 60) == part(0, 120));
+    for (int64_t every : {0, 30, 45}) {  // with a track too: record epochs 29, 59, ... / 44, 89
+      auto part = [&](int64_t a, int64_t n) {
+        return show_launches(plan_run(fl.data() + a, fx.data() + a, dl.data() + a, every, a, n, d));
+      };
+      CHECK(part(0, 60) + part(60, 60) == part(0, 120));
+    }
   }
 }
 
 // The rule once more, per epoch: an epoch's range ends with a BodyEfforts
-// epoch, a fix epoch, an arrival or a latch; its kernel is plan_epochs' (pair:
-// no pressure, and a stretch of kPairMinRun such epochs or the whole range); pd
-// from the state's decoupling when the epoch runs; EFFORTS, FIX, LATCH after it.
+// epoch, a fix epoch, an arrival, a latch or a record epoch ((e + 1) % every ==
+// 0; every 0: no track); its kernel is plan_epochs' (pair: no pressure, and a
+// stretch of kPairMinRun such epochs or the whole range); pd from the state's
+// decoupling when the epoch runs; EFFORTS, FIX, LATCH, RECORD after it.
 static EpochPlan naive_plan(const std::vector<uint32_t>& fl, const std::vector<uint32_t>& fx,
-                            const std::vector<uint32_t>& dl, int64_t first, EpochFacts f) {
+                            const std::vector<uint32_t>& dl, int64_t every, int64_t first, EpochFacts f) {
   EpochPlan p;
   const int64_t n = (int64_t)fl.size();
+  auto rec = [&](int64_t k) { return every > 0 && (first + k + 1) % every == 0; };
   std::vector<int> range_of((size_t)n);
   for (int64_t k = 0, r = 0; k < n; k++) {
     range_of[(size_t)k] = (int)r;
-    if ((fl[(size_t)k] & E) || fx[(size_t)k] || dl[(size_t)k]) r++;
+    if ((fl[(size_t)k] & E) || fx[(size_t)k] || dl[(size_t)k] || rec(k)) r++;
   }
   auto in_range = [&](int64_t a, int64_t k) { return a >= 0 && a < n && range_of[(size_t)a] == range_of[(size_t)k]; };
   std::vector<LaunchKind> label((size_t)n, EPOCH_ONE);
@@ -181,13 +127,15 @@ static EpochPlan naive_plan(const std::vector<uint32_t>& fl, const std::vector<u
     if (fl[i] & E) p.launches.push_back({EFFORTS, first + k, 1, 0, (fl[i] & VO) ? 1 : 0, fl[i]});
     if (fx[i] || (dl[i] & ARR)) p.launches.push_back({FIX, first + k, 1, 0, 0, fx[i] | (dl[i] & ARR)});
     if (dl[i] & LAT) p.launches.push_back({LATCH, first + k, 1, 0, 0, LAT});
+    if (rec(k)) p.launches.push_back({RECORD, first + k, 1, 0, 0, 0});
   }
   p.pdec = f.pdec;
   return p;
 }
 
-// the seeded random logs of plan_test.cpp: zero delayed flags give
-// plan_fix_epochs' plan exactly; random ones give the per-epoch restatement's
+// the seeded random logs of plan_test.cpp: zero or null delayed flags change
+// nothing, and with zero fix flags too the plan is plan_epochs' exactly; random
+// ones, with and without a track, give the per-epoch restatement's
 static void test_properties() {
   std::mt19937_64 rng(20261);
   std::uniform_real_distribution<double> u01(0.0, 1.0);
@@ -199,7 +147,7 @@ static void test_properties() {
   variants[4].persist = 0;
   variants[5].dof = 26, variants[5].q_simple = false, variants[5].q_params_diag = false;
   const double dens[] = {0.0, 0.002, 0.01, 0.05, 0.3};
-  int plans = 0, fixes = 0, latches = 0, pairs = 0;
+  int plans = 0, fixes = 0, latches = 0, records = 0, pairs = 0;
   for (const EpochFacts& f : variants)
     for (int it = 0; it < 400; it++, plans++) {
       const int64_t n = 1 + (int64_t)(rng() % 400), first = (it % 3) ? (int64_t)(rng() % 5000) : 0;
@@ -212,9 +160,10 @@ static void test_properties() {
       }
       for (uint32_t& w : fx)
         if (u01(rng) < df) w = 1u + (uint32_t)(rng() % 7);
-      const EpochPlan base = plan_fix_epochs(fl.data(), fx.data(), first, n, f);
-      if (!same(plan_delayed_epochs(fl.data(), fx.data(), dl.data(), first, n, f), base) ||
-          !same(plan_delayed_epochs(fl.data(), fx.data(), nullptr, first, n, f), base)) {
+      const EpochPlan base = plan_run(fl.data(), fx.data(), nullptr, 0, first, n, f);
+      if (!same(plan_run(fl.data(), fx.data(), dl.data(), 0, first, n, f), base) ||
+          !same(plan_run(fl.data(), nullptr, dl.data(), 0, first, n, f), plan_epochs(fl.data(), first, n, f)) ||
+          !same(base, naive_plan(fl, fx, dl, 0, first, f))) {
         std::printf("FAIL zero delayed flags, variant %d iteration %d\n", (int)(&f - variants), it);
         g_fail++;
       }
@@ -223,31 +172,43 @@ static void test_properties() {
         if (u01(rng) < dd) w |= ARR;
         if (u01(rng) < dd) w |= LAT;
       }
-      const EpochPlan p = plan_delayed_epochs(fl.data(), fx.data(), dl.data(), first, n, f);
+      const int64_t every = (it % 4 == 0) ? 0 : 1 + (int64_t)(rng() % 70);  // no track, or a stride of 1 .. 70
+      const EpochPlan p = plan_run(fl.data(), fx.data(), dl.data(), every, first, n, f);
+      auto rec = [&](int64_t e) { return every > 0 && (e + 1) % every == 0; };
       // structure: the epoch launches tile the range once in order; per event
-      // epoch at most one FIX and one LATCH, in the order EFFORTS, FIX, LATCH
+      // epoch at most one FIX, one LATCH and one RECORD, in the order EFFORTS, FIX, LATCH, RECORD
       int64_t next = first;
       bool ok = true;
-      size_t nfix = 0, nlatch = 0;
+      size_t nfix = 0, nlatch = 0, nrec = 0;
       for (size_t i = 0; i < p.launches.size() && ok; i++) {
         const Launch& l = p.launches[i];
         const size_t k = (size_t)(l.first - first);
         if (l.kind == FIX) {
           nfix++;
-          ok = i > 0 && p.launches[i - 1].kind != FIX && p.launches[i - 1].kind != LATCH && l.first == next - 1 &&
-               l.count == 1 && l.ev_any == (fx[k] | (dl[k] & ARR)) && l.ev_any != 0 &&
+          ok = i > 0 && p.launches[i - 1].kind != FIX && p.launches[i - 1].kind != LATCH &&
+               p.launches[i - 1].kind != RECORD && l.first == next - 1 && l.count == 1 &&
+               l.ev_any == (fx[k] | (dl[k] & ARR)) && l.ev_any != 0 &&
                ((fl[k] & E) != 0) == (p.launches[i - 1].kind == EFFORTS);
         } else if (l.kind == LATCH) {
           nlatch++;
           const LaunchKind before = i > 0 ? p.launches[i - 1].kind : LATCH;
-          ok = i > 0 && before != LATCH && l.first == next - 1 && l.count == 1 && (dl[k] & LAT) &&
+          ok = i > 0 && before != LATCH && before != RECORD && l.first == next - 1 && l.count == 1 && (dl[k] & LAT) &&
                (before == FIX) == ((fx[k] | (dl[k] & ARR)) != 0) && p.launches[i - 1].first + p.launches[i - 1].count - 1 == l.first;
+        } else if (l.kind == RECORD) {
+          nrec++;
+          // the last launch of its epoch: after its LATCH, else its FIX, else its EFFORTS, else the epoch launch
+          const LaunchKind before = i > 0 ? p.launches[i - 1].kind : RECORD;
+          const LaunchKind want = (dl[k] & LAT) ? LATCH : (fx[k] | (dl[k] & ARR)) ? FIX : (fl[k] & E) ? EFFORTS : EPOCH_ONE;
+          ok = i > 0 && l.first == next - 1 && l.count == 1 && rec(l.first) &&
+               (want == EPOCH_ONE ? (before == EPOCH_ONE || before == EPOCH_PAIR) : before == want) &&
+               p.launches[i - 1].first + p.launches[i - 1].count - 1 == l.first &&
+               (i + 1 == p.launches.size() || p.launches[i + 1].kind == EPOCH_ONE || p.launches[i + 1].kind == EPOCH_PAIR);
         } else if (l.kind == EFFORTS) {
           ok = l.first == next - 1;
         } else {
-          ok = l.first == next && l.count > 0;
+          ok = l.first == next && l.count > 0 && l.kind != EPOCH_DENSE;
           for (int64_t e = l.first; e + 1 < l.first + l.count; e++)
-            ok = ok && !fx[(size_t)(e - first)] && !dl[(size_t)(e - first)];
+            ok = ok && !fx[(size_t)(e - first)] && !dl[(size_t)(e - first)] && !rec(e);
           next = l.first + l.count;
           pairs += l.kind == EPOCH_PAIR;
         }
@@ -259,19 +220,125 @@ static void test_properties() {
       }
       fixes += (int)nfix;
       latches += (int)nlatch;
-      ok = ok && next == first + n && nfix == want_fix && nlatch == want_latch;
-      if (!ok || !same(p, naive_plan(fl, fx, dl, first, f))) {
-        std::printf("FAIL delayed plan property, variant %d iteration %d:\n  got   %s\n  naive %s\n",
-                    (int)(&f - variants), it, show(p).c_str(), show(naive_plan(fl, fx, dl, first, f)).c_str());
+      records += (int)nrec;
+      ok = ok && next == first + n && nfix == want_fix && nlatch == want_latch &&
+           (int64_t)nrec == (every > 0 ? track_records(first, n, every) : 0);
+      if (!ok || !same(p, naive_plan(fl, fx, dl, every, first, f))) {
+        std::printf("FAIL delayed plan property, variant %d iteration %d (every %lld):\n  got   %s\n  naive %s\n",
+                    (int)(&f - variants), it, (long long)every, show(p).c_str(),
+                    show(naive_plan(fl, fx, dl, every, first, f)).c_str());
         g_fail++;
       }
     }
-  CHECK(plans >= 2000 && fixes > 2000 && latches > 2000 && pairs > 200);
+  CHECK(plans >= 2000 && fixes > 2000 && latches > 2000 && records > 2000 && pairs > 200);
+}
+
+// A dense handle (the literal kernels): one fused launch per epoch, then the
+// epoch's events in the same order; no EFFORTS launch (the fused epoch holds
+// it), host_flags not read, never parameter-decoupled afterwards
+static void test_dense() {
+  EpochFacts d = defaults();
+  d.dense = true;
+  const auto fl = flags(12, IMU, {{3, E}, {5, E | VO}, {8, P}});
+  const auto fx = flags(12, 0, {{5, XY | Z | GEO}, {11, GEO}});
+  const auto dl = flags(12, 0, {{5, ARR | LAT}});
+  const char* want =
+      "DENSE[0,1) DENSE[1,2) DENSE[2,3) DENSE[3,4) DENSE[4,5) DENSE[5,6) FIX(5,m=15) LATCH(5) REC(5) "
+      "DENSE[6,7) DENSE[7,8) DENSE[8,9) DENSE[9,10) DENSE[10,11) DENSE[11,12) FIX(11,m=4) REC(11) pdec=0";
+  const EpochPlan p = plan_run(fl.data(), fx.data(), dl.data(), 6, 0, 12, d);
+  expect_plan(p, want, __LINE__);
+  CHECK(!p.pdec);
+  for (const Launch& l : p.launches) CHECK(l.kind != EFFORTS && l.kind != EPOCH_ONE && l.kind != EPOCH_PAIR && l.count == 1);
+  expect_plan(plan_run(nullptr, fx.data(), dl.data(), 6, 0, 12, d), want, __LINE__);
+  // no events: the epochs alone; first > 0; an empty range
+  expect_plan(plan_run(nullptr, nullptr, nullptr, 0, 0, 3, d), "DENSE[0,1) DENSE[1,2) DENSE[2,3) pdec=0", __LINE__);
+  expect_plan(plan_run(nullptr, fx.data() + 4, dl.data() + 4, 6, 4, 3, d),
+              "DENSE[4,5) DENSE[5,6) FIX(5,m=15) LATCH(5) REC(5) DENSE[6,7) pdec=0", __LINE__);
+  expect_plan(plan_run(nullptr, nullptr, nullptr, 6, 7, 0, d), "pdec=0", __LINE__);
+  // the same log on a PSP handle: the efforts epochs end launches and have their EFFORTS launch
+  expect_plan(plan_run(fl.data(), fx.data(), dl.data(), 6, 0, 12, defaults()),
+              "PAIR[0,4)pd EFFORTS(3,vo=0) ONE[4,6) EFFORTS(5,vo=1) FIX(5,m=15) LATCH(5) REC(5) ONE[6,12) FIX(11,m=4) "
+              "REC(11) pdec=0",
+              __LINE__);
+}
+
+// delayed_events on a 10-epoch log with 3 rows, over the range [3, 8): the
+// example's flag array and latch list, then each defect alone
+static void test_delayed_events() {
+  // row r latches after epoch L[r] and arrives at the epoch e with index[e] = r
+  const std::vector<int32_t> L = {6, 1, 4}, index = {-1, -1, -1, 1, -1, -1, -1, 2, -1, 0};
+  double rows[1] = {0.0};  // stands for the device arrays: tested for null, never read
+  uwvk_pose_delayed ok{};
+  ok.index = index.data(), ok.latch_epoch = L.data(), ok.xy = rows, ok.latched = rows, ok.n = 3;
+  DelayedEvents ev;
+  CHECK(delayed_events(&ok, 10, 3, 5, &ev));
+  // row 1's latch (epoch 1) and row 0's arrival (epoch 9) lie outside the range
+  CHECK((ev.flags == std::vector<uint32_t>{ARR, LAT, 0, LAT, ARR}));
+  CHECK((ev.latches == std::vector<std::pair<int64_t, int32_t>>{{4, 2}, {6, 0}}));
+  CHECK(delayed_events(&ok, 10, 0, 10, &ev));
+  CHECK((ev.flags == std::vector<uint32_t>{0, LAT, 0, ARR, LAT, 0, LAT, ARR, 0, ARR}));
+  CHECK((ev.latches == std::vector<std::pair<int64_t, int32_t>>{{1, 1}, {4, 2}, {6, 0}}));
+  CHECK(delayed_events(&ok, 10, 8, 0, &ev) && ev.flags.empty() && ev.latches.empty());
+  auto with = [](std::vector<int32_t> v, int64_t e, int32_t x) {
+    v[(size_t)e] = x;
+    return v;
+  };
+  auto rejected = [&](const uwvk_pose_delayed& d, int64_t first, int64_t count) {
+    DelayedEvents out;
+    return !delayed_events(&d, 10, first, count, &out);
+  };
+  uwvk_pose_delayed d = ok;
+  // an index below -1 or >= n, at an epoch of the range only
+  for (int32_t v : {-2, 3, 1 << 20}) {
+    const auto bad = with(index, 5, v);
+    d = ok, d.index = bad.data();
+    CHECK(rejected(d, 3, 5) && rejected(d, 5, 1) && !rejected(d, 6, 2) && !rejected(d, 3, 2));
+  }
+  d = ok, d.n = 2;  // row 2, arriving at epoch 7, is gone
+  CHECK(rejected(d, 3, 5) && !rejected(d, 3, 4));
+  // a latch epoch below -1 or >= epochs, whatever the range; -1 is a caller-filled row
+  for (int32_t v : {-2, 10, 1 << 20}) {
+    const auto bad = with(L, 2, v);
+    d = ok, d.latch_epoch = bad.data();
+    CHECK(rejected(d, 3, 5) && rejected(d, 0, 0));
+  }
+  {
+    const auto filled = with(L, 2, -1);
+    d = ok, d.latch_epoch = filled.data();
+    CHECK(delayed_events(&d, 10, 3, 5, &ev) && (ev.flags == std::vector<uint32_t>{ARR, 0, 0, LAT, ARR}));
+  }
+  // an arrival at or before its row's latch (row 2 arrives at epoch 7), when the arrival is in the range
+  for (int32_t v : {7, 8}) {
+    const auto bad = with(L, 2, v);
+    d = ok, d.latch_epoch = bad.data();
+    CHECK(rejected(d, 3, 5) && rejected(d, 7, 1) && !rejected(d, 3, 4));
+  }
+  d = ok, d.n = -1;
+  CHECK(rejected(d, 3, 5) && rejected(d, 0, 0));
+  // n > 0 and a null array, each of the four
+  d = ok, d.index = nullptr;
+  CHECK(rejected(d, 3, 5) && rejected(d, 0, 0));
+  d = ok, d.latch_epoch = nullptr;
+  CHECK(rejected(d, 3, 5));
+  d = ok, d.xy = nullptr;
+  CHECK(rejected(d, 3, 5));
+  d = ok, d.latched = nullptr;
+  CHECK(rejected(d, 3, 5));
+  // n == 0: no arrays needed, no events; an index array is still checked
+  d = uwvk_pose_delayed{};
+  CHECK(delayed_events(&d, 10, 3, 5, &ev) && (ev.flags == std::vector<uint32_t>(5, 0u)) && ev.latches.empty());
+  const std::vector<int32_t> none(10, -1);
+  d.index = none.data();
+  CHECK(!rejected(d, 0, 10));
+  d.index = index.data();
+  CHECK(rejected(d, 0, 10));
 }
 
 int main() {
   test_cases();
   test_properties();
+  test_dense();
+  test_delayed_events();
   if (g_fail) std::printf("%d checks failed\n", g_fail);
   else std::printf("delayed_plan_test: ok\n");
   return g_fail ? 1 : 0;

@@ -1,72 +1,16 @@
-// fix_plan_test.cpp — the launch plan of uwvk_pose_run_log_fixes
-// (plan_fix_epochs, csrc/uwvk_plan.hpp) on the CPU: without fix flags it is
+// fix_plan_test.cpp — the launch plan of uwvk_pose_run_log_fixes (plan_run with
+// fix flags, csrc/uwvk_plan.hpp) on the CPU: without fix flags it is
 // plan_epochs' plan; a fix epoch ends a launch and is followed by one FIX
 // launch, after the epoch's EFFORTS launch; a fix leaves pd / pair on; track
-// cuts compose with fix cuts; and a per-epoch restatement of the rule over
-// seeded random flag sets.  Exit 0 = all checks hold.
-#include <cstdio>
+// records compose with fixes; a per-epoch restatement of the rule over seeded
+// random flag sets; and the argument check fixes_valid.  Exit 0 = all checks hold.
 #include <random>
-#include <string>
 
-#include "../../slam-uwv_kalman_filters_amd/csrc/uwvk_plan.hpp"
-
-using namespace uwvk;
-
-static int g_fail = 0;
-#define CHECK(c)                                               \
-  do {                                                         \
-    if (!(c)) {                                                \
-      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c); \
-      g_fail++;                                                \
-    }                                                          \
-  } while (0)
-
-constexpr uint32_t IMU = UWVK_EV_ACC, P = UWVK_EV_PRESSURE, A = UWVK_EV_ADCP, E = UWVK_EV_EFFORTS,
-                   VO = UWVK_EV_EFFORTS_VELOCITY_ONLY;
-constexpr uint32_t XY = UWVK_FIX_XY, Z = UWVK_FIX_Z, GEO = UWVK_FIX_GEO;
-
-// dof 53, an even batch, every option at its default, a decoupled state and a
-// simple, parameter-diagonal Q (plan_test.cpp's defaults)
-static EpochFacts defaults() { return {53, 64, 1, 1, 1, 0, false, true, true, true}; }
-
-// "PAIR[0,60)pd EFFORTS(59,vo=0) FIX(59,m=3) ONE[60,120) pdec=0"
-static std::string show(const EpochPlan& p) {
-  std::string s;
-  for (const Launch& l : p.launches) {
-    if (l.kind == EFFORTS) s += "EFFORTS(" + std::to_string(l.first) + ",vo=" + std::to_string(l.vo) + ") ";
-    else if (l.kind == FIX) s += "FIX(" + std::to_string(l.first) + ",m=" + std::to_string(l.ev_any) + ") ";
-    else
-      s += std::string(l.kind == EPOCH_PAIR ? "PAIR[" : "ONE[") + std::to_string(l.first) + "," +
-           std::to_string(l.first + l.count) + ")" + (l.pd ? "pd " : " ");
-  }
-  return s + "pdec=" + std::to_string((int)p.pdec);
-}
-
-using Ev = std::initializer_list<std::pair<int64_t, uint32_t>>;
-static std::vector<uint32_t> flags(int64_t n, uint32_t base, Ev ev = {}) {
-  std::vector<uint32_t> f((size_t)n, base);
-  for (auto& e : ev) f[(size_t)e.first] |= e.second;
-  return f;
-}
-
-static bool same(const EpochPlan& a, const EpochPlan& b) {
-  if (a.pdec != b.pdec || a.launches.size() != b.launches.size()) return false;
-  for (size_t i = 0; i < a.launches.size(); i++) {
-    const Launch &x = a.launches[i], &y = b.launches[i];
-    if (x.kind != y.kind || x.first != y.first || x.count != y.count || x.pd != y.pd || x.vo != y.vo ||
-        x.ev_any != y.ev_any)
-      return false;
-  }
-  return true;
-}
+#include "plan_check.hpp"
 
 static void expect(const std::vector<uint32_t>& f, const std::vector<uint32_t>& fx, const EpochFacts& facts,
                    const char* want, int line) {
-  const std::string got = show(plan_fix_epochs(f.data(), fx.data(), 0, (int64_t)f.size(), facts));
-  if (got != want) {
-    std::printf("FAIL line %d:\n  got  %s\n  want %s\n", line, got.c_str(), want);
-    g_fail++;
-  }
+  expect_plan(plan_run(f.data(), fx.data(), nullptr, 0, 0, (int64_t)f.size(), facts), want, line);
 }
 #define EXPECT(f, fx, facts, want) expect(f, fx, facts, want, __LINE__)
 
@@ -101,29 +45,21 @@ static void test_cases() {
   {
     const auto fx = flags(100, 0, {{48, GEO}});
     const auto fl = flags(100, IMU);
-    CHECK(show(plan_fix_epochs(fl.data(), fx.data(), 1000, 100, d)) ==
+    CHECK(show(plan_run(fl.data(), fx.data(), nullptr, 0, 1000, 100, d)) ==
           "PAIR[1000,1049)pd FIX(1048,m=4) PAIR[1049,1100)pd pdec=1");
-    CHECK(same(plan_fix_epochs(fl.data(), nullptr, 1000, 100, d), plan_epochs(fl.data(), 1000, 100, d)));
-    CHECK(show(plan_fix_epochs(nullptr, nullptr, 7, 0, d)) == "pdec=1");
+    CHECK(same(plan_run(fl.data(), nullptr, nullptr, 0, 1000, 100, d), plan_epochs(fl.data(), 1000, 100, d)));
+    CHECK(show(plan_run(nullptr, nullptr, nullptr, 0, 7, 0, d)) == "pdec=1");
     EpochFacts g = d;
     g.pdec = false;
-    CHECK(show(plan_fix_epochs(nullptr, nullptr, 7, 0, g)) == "pdec=0");
+    CHECK(show(plan_run(nullptr, nullptr, nullptr, 0, 7, 0, g)) == "pdec=0");
   }
 }
 
-// the launches of a tracked run with fixes, as run_log queues them: per track
-// segment the plan of plan_fix_epochs, then the record ("REC(e)")
+// the launches of a tracked run with fixes, as run_log queues them: the
+// record ("REC(e)") after its epoch's launches
 static std::string tracked(const std::vector<uint32_t>& fl, const std::vector<uint32_t>& fx, int64_t first,
                            int64_t count, int64_t every, EpochFacts f) {
-  std::string s;
-  for (const TrackSegment& seg : track_segments(first, count, every)) {
-    const EpochPlan p = plan_fix_epochs(fl.data() + seg.first, fx.data() + seg.first, seg.first, seg.count, f);
-    f.pdec = p.pdec;
-    const std::string t = show(p);
-    s += t.substr(0, t.rfind("pdec="));
-    if (seg.record) s += "REC(" + std::to_string(seg.first + seg.count - 1) + ") ";
-  }
-  return s;
+  return show_launches(plan_run(fl.data() + first, fx.data() + first, nullptr, every, first, count, f));
 }
 
 static void test_track() {
@@ -205,8 +141,8 @@ static void test_properties() {
       }
       const EpochPlan base = plan_epochs(fl.data(), first, n, f);
       const std::vector<uint32_t> none((size_t)n, 0u);
-      if (!same(plan_fix_epochs(fl.data(), none.data(), first, n, f), base) ||
-          !same(plan_fix_epochs(fl.data(), nullptr, first, n, f), base)) {
+      if (!same(plan_run(fl.data(), none.data(), nullptr, 0, first, n, f), base) ||
+          !same(plan_run(fl.data(), nullptr, nullptr, 0, first, n, f), base)) {
         std::printf("FAIL zero fix flags, variant %d iteration %d\n", (int)(&f - variants), it);
         g_fail++;
       }
@@ -214,7 +150,7 @@ static void test_properties() {
       std::vector<uint32_t> fx((size_t)n, 0u);
       for (uint32_t& w : fx)
         if (u01(rng) < df) w = 1u + (uint32_t)(rng() % 7);
-      const EpochPlan p = plan_fix_epochs(fl.data(), fx.data(), first, n, f);
+      const EpochPlan p = plan_run(fl.data(), fx.data(), nullptr, 0, first, n, f);
       // structure: the epoch launches tile the range once in order; a FIX entry
       // per flagged epoch, right after the launch that ends with it (or its EFFORTS)
       int64_t next = first;
@@ -249,10 +185,60 @@ static void test_properties() {
   CHECK(plans >= 2000 && fixes > 2000 && pairs > 200);
 }
 
+// fixes_valid on a 10-epoch log with 3 rows per kind: the example is accepted,
+// each defect alone is rejected, and only inside [first, first + count)
+static void test_fixes_valid() {
+  const auto fl = flags(10, 0, {{2, XY}, {5, XY | Z | GEO}, {9, GEO}});
+  const std::vector<int32_t> xi = {-1, -1, 0, -1, -1, 2, -1, -1, -1, -1}, zi = {-1, -1, -1, -1, -1, 1, -1, -1, -1, -1},
+                             gi = {-1, -1, -1, -1, -1, 0, -1, -1, -1, 2};
+  const double rows[1] = {0.0};  // stands for the device arrays: tested for null, never read
+  uwvk_pose_fixes ok{};
+  ok.host_flags = fl.data();
+  ok.xy_index = xi.data(), ok.xy = rows, ok.n_xy = 3;
+  ok.z_index = zi.data(), ok.z = rows, ok.n_z = 3;
+  ok.geo_index = gi.data(), ok.geo = rows, ok.n_geo = 3;
+  CHECK(fixes_valid(&ok, 0, 10) && fixes_valid(&ok, 3, 4) && fixes_valid(&ok, 10, 0));
+  // the epoch whose entry is changed, the changed struct
+  auto bad = [&](int64_t e, const uwvk_pose_fixes& f) {
+    // rejected over every range that holds the epoch, accepted beside it
+    return !fixes_valid(&f, 0, 10) && !fixes_valid(&f, e, 1) && fixes_valid(&f, 0, e) && fixes_valid(&f, e + 1, 9 - e);
+  };
+  auto with = [](std::vector<int32_t> v, int64_t e, int32_t x) {
+    v[(size_t)e] = x;
+    return v;
+  };
+  uwvk_pose_fixes f = ok;
+  const auto neg = with(xi, 2, -1), past = with(gi, 9, 3), far = with(zi, 5, 1 << 20);
+  f.xy_index = neg.data();  // a negative index at a flagged epoch
+  CHECK(bad(2, f));
+  f = ok, f.geo_index = past.data();  // an index >= n
+  CHECK(bad(9, f));
+  f = ok, f.z_index = far.data();
+  CHECK(bad(5, f));
+  f = ok, f.n_xy = 2;  // row 2 is gone
+  CHECK(bad(5, f));
+  f = ok, f.z_index = nullptr;  // a flagged kind without its index array
+  CHECK(bad(5, f));
+  f = ok, f.z = nullptr;  // ... without its rows
+  CHECK(bad(5, f));
+  f = ok, f.xy = nullptr;  // (flagged at epochs 2 and 5)
+  CHECK(!fixes_valid(&f, 0, 10) && !fixes_valid(&f, 2, 1) && !fixes_valid(&f, 5, 1) && fixes_valid(&f, 6, 4));
+  const auto outside = flags(10, 0, {{2, XY}, {5, XY | Z | GEO}, {7, 0x8u}, {9, GEO}});
+  f = ok, f.host_flags = outside.data();  // a flag bit outside UWVK_FIX_*
+  CHECK(bad(7, f));
+  f = ok, f.host_flags = nullptr;
+  CHECK(!fixes_valid(&f, 0, 10) && !fixes_valid(&f, 0, 0));
+  // an unflagged kind needs no arrays, an unflagged epoch no valid index
+  const auto only_z = flags(10, 0, {{5, Z}});
+  f = ok, f.host_flags = only_z.data(), f.xy_index = nullptr, f.xy = nullptr, f.geo = nullptr, f.n_geo = 0;
+  CHECK(fixes_valid(&f, 0, 10));
+}
+
 int main() {
   test_cases();
   test_track();
   test_properties();
+  test_fixes_valid();
   if (g_fail) std::printf("%d checks failed\n", g_fail);
   else std::printf("fix_plan_test: ok\n");
   return g_fail ? 1 : 0;

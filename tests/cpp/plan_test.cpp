@@ -3,55 +3,18 @@
 // and a property check against a naive restatement of the rule), the grid /
 // tail geometry, the process-noise tables and the parameter-block scan.
 // Exit 0 = all checks hold.
-#include <cstdio>
 #include <random>
-#include <string>
 
-#include "../../slam-uwv_kalman_filters_amd/csrc/uwvk_plan.hpp"
+#include "plan_check.hpp"
 #include "../../slam-uwv_kalman_filters_amd/csrc/uwvk_host.hpp"
 
-using namespace uwvk;
-
-static int g_fail = 0;
-#define CHECK(c)                                                   \
-  do {                                                             \
-    if (!(c)) {                                                    \
-      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);     \
-      g_fail++;                                                    \
-    }                                                              \
-  } while (0)
-
-constexpr uint32_t IMU = UWVK_EV_ACC, P = UWVK_EV_PRESSURE, A = UWVK_EV_ADCP, E = UWVK_EV_EFFORTS,
-                   VO = UWVK_EV_EFFORTS_VELOCITY_ONLY;
-
-// dof 53, an even batch, every option at its default, a decoupled state and a
-// simple, parameter-diagonal Q
-static EpochFacts defaults() { return {53, 64, 1, 1, 1, 0, false, true, true, true}; }
-
-// "PAIR[0,100) ONE[100,101)pd EFFORTS(59,vo=0) ... pdec=1"
-static std::string show(const EpochPlan& p) {
-  std::string s;
-  for (const Launch& l : p.launches) {
-    if (l.kind == EFFORTS) s += "EFFORTS(" + std::to_string(l.first) + ",vo=" + std::to_string(l.vo) + ") ";
-    else
-      s += std::string(l.kind == EPOCH_PAIR ? "PAIR[" : "ONE[") + std::to_string(l.first) + "," +
-           std::to_string(l.first + l.count) + ")" + (l.pd ? "pd " : " ");
-  }
-  return s + "pdec=" + std::to_string((int)p.pdec);
-}
-
-static std::vector<uint32_t> flags(int64_t n, std::initializer_list<std::pair<int64_t, uint32_t>> ev = {}) {
-  std::vector<uint32_t> f((size_t)n, IMU);
-  for (auto& e : ev) f[(size_t)e.first] |= e.second;
-  return f;
-}
+// an all-IMU log of n epochs, ev's bits ORed in
+static std::vector<uint32_t> flags(int64_t n, Ev ev = {}) { return flags(n, IMU, ev); }
 
 static void expect(const std::vector<uint32_t>& f, const EpochFacts& facts, const char* want, int line) {
-  const std::string got = show(plan_epochs(f.data(), 0, (int64_t)f.size(), facts));
-  if (got != want) {
-    std::printf("FAIL line %d:\n  got  %s\n  want %s\n", line, got.c_str(), want);
-    g_fail++;
-  }
+  expect_plan(plan_epochs(f.data(), 0, (int64_t)f.size(), facts), want, line);
+  // a call without events is plan_epochs' plan
+  expect_plan(plan_run(f.data(), nullptr, nullptr, 0, 0, (int64_t)f.size(), facts), want, line);
 }
 #define EXPECT(f, facts, want) expect(f, facts, want, __LINE__)
 
@@ -153,17 +116,6 @@ static EpochPlan naive_plan(const std::vector<uint32_t>& fl, int64_t first, Epoc
   return p;
 }
 
-static bool same(const EpochPlan& a, const EpochPlan& b) {
-  if (a.pdec != b.pdec || a.launches.size() != b.launches.size()) return false;
-  for (size_t i = 0; i < a.launches.size(); i++) {
-    const Launch &x = a.launches[i], &y = b.launches[i];
-    if (x.kind != y.kind || x.first != y.first || x.count != y.count || x.pd != y.pd || x.vo != y.vo ||
-        x.ev_any != y.ev_any)
-      return false;
-  }
-  return true;
-}
-
 static void test_plan_properties() {
   std::mt19937_64 rng(20260);
   std::uniform_real_distribution<double> u01(0.0, 1.0);
@@ -217,7 +169,7 @@ static void test_plan_properties() {
         }
       }
       ok = ok && next == first + n;
-      if (!ok || !same(p, naive_plan(fl, first, f))) {
+      if (!ok || !same(p, naive_plan(fl, first, f)) || !same(p, plan_run(fl.data(), nullptr, nullptr, 0, first, n, f))) {
         std::printf("FAIL plan property, variant %d iteration %d:\n  got  %s\n  naive %s\n", (int)(&f - variants), it,
                     show(p).c_str(), show(naive_plan(fl, first, f)).c_str());
         g_fail++;

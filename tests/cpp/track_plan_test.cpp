@@ -1,9 +1,9 @@
-// track_plan_test.cpp — the record cuts of uwvk_pose_run_log_track
-// (track_segments / track_records, csrc/uwvk_plan.hpp) on the CPU, over fixed
-// and seeded random (first, count, every): the segments tile the range in
-// order, each but possibly the last ends at a record epoch, their number is
-// the closed form, and a range split anywhere gives the two halves' records
-// one after the other.  Exit 0 = all checks hold.
+// track_plan_test.cpp — the record cuts of uwvk_pose_run_log_track (plan_run's
+// RECORD launches / track_records, csrc/uwvk_plan.hpp) on the CPU, over fixed
+// and seeded random (first, count, every) on an all-IMU log: the pieces between
+// records tile the range in order, each but possibly the last ends at a record
+// epoch, their number is the closed form, and a range split anywhere gives the
+// two halves' records one after the other.  Exit 0 = all checks hold.
 #include <cstdio>
 #include <random>
 
@@ -21,19 +21,46 @@ static int g_fail = 0;
     }                                                                                                         \
   } while (0)
 
+// [first, first + count) as plan_run cuts it for the track alone: the epochs
+// its launches cover up to and including each RECORD (record), then what is
+// left at the range's end without one
+struct Piece {
+  int64_t first, count;
+  bool record;
+};
+static std::vector<Piece> record_pieces(int64_t first, int64_t count, int64_t every) {
+  const std::vector<uint32_t> imu((size_t)count, UWVK_EV_ACC);
+  const EpochPlan p = plan_run(imu.data(), nullptr, nullptr, every, first, count,
+                               {53, 63, 1, 0, 1, 0, false, true, true, true});  // no pair kernel: one launch per piece
+  std::vector<Piece> s;
+  int64_t e = first, next = first;  // the open piece is [e, next)
+  for (const Launch& l : p.launches) {
+    if (l.kind == RECORD) {
+      if (l.first != next - 1 || next == e) return {};  // a record not at the end of what ran: no valid cut
+      s.push_back({e, next - e, true});
+      e = next;
+    } else {
+      if (l.first != next || l.count <= 0 || (l.kind != EPOCH_ONE && l.kind != EPOCH_PAIR)) return {};
+      next += l.count;
+    }
+  }
+  if (next > e) s.push_back({e, next - e, false});
+  return s;
+}
+
 // the record epochs of a range, from its segments
 static std::vector<int64_t> records(int64_t first, int64_t count, int64_t every) {
   std::vector<int64_t> r;
-  for (const TrackSegment& s : track_segments(first, count, every))
+  for (const Piece& s : record_pieces(first, count, every))
     if (s.record) r.push_back(s.first + s.count - 1);
   return r;
 }
 
 static void check_case(int64_t first, int64_t count, int64_t every) {
-  const std::vector<TrackSegment> segs = track_segments(first, count, every);
+  const std::vector<Piece> segs = record_pieces(first, count, every);
   int64_t e = first, nrec = 0;
   for (size_t k = 0; k < segs.size(); k++) {
-    const TrackSegment& s = segs[k];
+    const Piece& s = segs[k];
     CHECK(s.first == e && s.count > 0);  // in order, no gap, no empty segment
     e = s.first + s.count;
     if (s.record) nrec++;
@@ -76,7 +103,7 @@ int main() {
   // large epochs: no 32-bit arithmetic
   {
     const int64_t first = (int64_t(1) << 33) + 5, count = 1000, every = 300;
-    const std::vector<TrackSegment> segs = track_segments(first, count, every);
+    const std::vector<Piece> segs = record_pieces(first, count, every);
     CHECK(!segs.empty() && segs.front().first == first && segs.back().first + segs.back().count == first + count);
     CHECK((int64_t)records(first, count, every).size() == track_records(first, count, every));
   }

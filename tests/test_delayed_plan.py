@@ -1,11 +1,12 @@
-"""The launch plan of uwvk_pose_run_log_delayed (plan_delayed_epochs in
+"""The launch plan of uwvk_pose_run_log_delayed (plan_run with delayed flags in
 csrc/uwvk_plan.hpp) on the CPU: tests/cpp/delayed_plan_test.cpp checks that zero
-delayed flags give plan_fix_epochs' plan, the fixed cases (a latch on the first
-and last epoch, one epoch before an arrival, with an arrival of another row, on
-a BodyEfforts, pressure and fix epoch with FIX before LATCH, pdec after a full
-BodyEfforts), and a per-epoch restatement over seeded random flag sets.  No
-device, no libuwvk.so.  Built and run twice, the second time under the address
-and undefined-behaviour sanitizers."""
+delayed and fix flags give plan_epochs' plan, the fixed cases (a latch on the
+first and last epoch, one epoch before an arrival, with an arrival of another
+row, on a BodyEfforts, pressure and fix epoch with FIX before LATCH, pdec after a
+full BodyEfforts), a per-epoch restatement over seeded random flag sets and
+track strides, the plan of a dense handle, and the argument check
+delayed_events.  No device, no libuwvk.so.  Built and run twice, the second time
+under the address and undefined-behaviour sanitizers."""
 import os
 import subprocess
 

@@ -1,9 +1,10 @@
-"""The launch plan of uwvk_pose_run_log_fixes (plan_fix_epochs in
+"""The launch plan of uwvk_pose_run_log_fixes (plan_run with fix flags in
 csrc/uwvk_plan.hpp) on the CPU: tests/cpp/fix_plan_test.cpp checks that zero fix
 flags give plan_epochs' plan, the fixed cases (first / last / adjacent epochs, a
-BodyEfforts, pressure and track record epoch, pd after a fix), and a per-epoch
-restatement over seeded random flag sets.  No device, no libuwvk.so.  Built and
-run twice, the second time under the address and undefined-behaviour sanitizers."""
+BodyEfforts, pressure and track record epoch, pd after a fix), a per-epoch
+restatement over seeded random flag sets, and the argument check fixes_valid.
+No device, no libuwvk.so.  Built and run twice, the second time under the
+address and undefined-behaviour sanitizers."""
 import os
 import subprocess
 

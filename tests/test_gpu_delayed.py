@@ -169,6 +169,25 @@ def test_delayed_bitwise_literal(eng):
     np.testing.assert_array_equal(got["dacc"], [3] * 6)
 
 
+def test_delayed_literal_with_track(eng):
+    """The literal path with a track and events together: every = 6 puts the
+    records on epoch 5 (three fixes, an arrival and a latch) and on epoch 11 (a
+    fix and an arrival), each taken after all of its epoch's launches."""
+    from uwvk import synth
+    log = synth.make_pose_log(6, 12, "C3")
+    fx = make_fixes(log, [(5, XY | Z | GEO), (11, GEO)])
+    dl = make_delayed(log, [(0, 5), (5, 6), (6, 11)])
+    ga, gb = (_handle(eng, log, literal=True) for _ in range(2))
+    got = _in_run(eng, ga, log, fx, dl, every=6)
+    ref = _by_cuts(eng, gb, log, fx, dl, records=(5, 11))
+    np.testing.assert_array_equal(got["epochs"], (5, 11))
+    _same(got, ref, ("mean", "variance") + NAMES)
+    assert got["pd"] == 0 and not got["status"].any()
+    np.testing.assert_array_equal(got["dacc"], [3] * 6)
+    # row 1 latches on the record epoch 5: that record's position, after the epoch's fixes and arrival
+    np.testing.assert_array_equal(got["latched"][1], got["mean"][0][:, 0:2])
+
+
 def test_delayed_with_track_and_split_ranges(eng):
     """every = 30: one call and the calls [0, 60), [60, 120) on one
     DevicePoseDelayed give the cut run's records, state and counts.  Row (58, 60)

@@ -1,6 +1,7 @@
-"""The record cuts of uwvk_pose_run_log_track (track_segments / track_records in
-csrc/uwvk_plan.hpp) on the CPU: tests/cpp/track_plan_test.cpp checks, over fixed
-and seeded random (first, count, every), that the segments tile the range, end
+"""The record cuts of uwvk_pose_run_log_track (plan_run's RECORD launches /
+track_records in csrc/uwvk_plan.hpp) on the CPU: tests/cpp/track_plan_test.cpp
+checks, over fixed and seeded random (first, count, every), that the segments
+between records tile the range, end
 at record epochs, number what the closed form says and compose across a split
 of the range.  No device, no libuwvk.so.  Built and run twice, the second time
 under the address and undefined-behaviour sanitizers."""
