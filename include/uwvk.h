@@ -55,7 +55,8 @@ extern "C" {
  *      point changed): uwvk_pose_fixes, UWVK_FIX_*, uwvk_pose_run_log_fixes,
  *      uwvk_schedule_fixes; uwvk_pose_delayed, uwvk_pose_run_log_delayed,
  *      uwvk_schedule_delayed; uwvk_bottom_log, uwvk_bottom_track, UWVK_BEV_*,
- *      uwvk_bottom_log_check, uwvk_bottom_run_log, uwvk_bottom_synchronize. */
+ *      uwvk_bottom_log_check, uwvk_bottom_run_log, uwvk_bottom_synchronize;
+ *      uwvk_vel_get_status. */
 #define UWVK_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
@@ -72,7 +73,7 @@ typedef enum uwvk_status {
                         returned by the next uwvk_pose_synchronize / uwvk_pose_run_log */
 } uwvk_status;
 
-/* per-instance status bits (uwvk_pose_get_status / uwvk_vel_get_status) */
+/* per-instance status bits (the *_get_status getters of every filter family) */
 #define UWVK_ST_NOTPD 0x1u    /* Cholesky of Sigma failed (non-positive pivot) */
 #define UWVK_ST_NAN 0x2u      /* non-finite measurement skipped for this instance */
 #define UWVK_ST_NONFINITE 0x4u/* non-finite state after a step */
@@ -778,6 +779,20 @@ uwvk_status uwvk_vel_update_pressure(uwvk_vel* h, const double* mu, const double
 uwvk_status uwvk_vel_get_state(uwvk_vel* h, double* x, double* P);
 /* motion-model side state: batch*13 {p(3), q(4: w,x,y,z), v(3), w(3)} */
 uwvk_status uwvk_vel_get_model_state(uwvk_vel* h, double* out);
+/* Per-instance status words: waits for the handle's stream, copies batch words
+ * and, if clear, zeroes the device words (as the pose and bottom getters do).
+ * NULL handle or status: UWVK_EINVAL.  The only bit VelocityUKF raises today:
+ *  - UWVK_ST_NOTPD, sticky until cleared: the Cholesky factorisation at the
+ *    start of a predict or an update (single calls and every run_log epoch
+ *    alike) met a non-positive pivot.  The step is NOT skipped: the flagged
+ *    instance's state and covariance are overwritten and unspecified from then
+ *    on (unlike BottomUKF, which keeps the state it had); re-initialise it.
+ *    The other instances are unaffected.
+ *  - A non-finite sample in a device-resident log is not screened (the single
+ *    calls reject one with UWVK_ENAN; run_log cannot): it enters that
+ *    instance's state and surfaces as UWVK_ST_NOTPD at the next step's
+ *    factorisation, so a bad sample in a run's LAST step leaves no bit. */
+uwvk_status uwvk_vel_get_status(uwvk_vel* h, uint32_t* status, int clear);
 
 typedef struct uwvk_vel_log {
   int64_t epochs;

@@ -594,17 +594,24 @@ class VelTwin:
         self.gyro = np.asarray(w, float)
         self.model[10:13] = self.gyro
 
-    def predict(self, dt):
-        q = self.model[3:7]
+    def set_efforts(self, tau):
+        self.tau = np.asarray(tau, float)
 
-        def g(X):
-            s = np.concatenate([np.zeros((len(X), 3)), np.broadcast_to(q, (len(X), 4)), X[:, :3],
-                                np.broadcast_to(self.gyro, (len(X), 3))], 1)
-            n = self.uwv.rk4(s, self.tau, dt)
-            v = X[:, :3] + (n[:, 7:10] - X[:, :3])
-            z = X[:, 3] + dt * qrot(q, v)[:, 2]
-            return np.concatenate([v, z[:, None]], 1)
-        self.mu, self.P = ukf_predict(self.lay, self.mu, self.P, g, dt * self.Q)
+    def set_process_noise(self, Q):
+        self.Q = np.array(Q, float)
+
+    def process(self, X, dt):
+        """processMotionModel (VelocityUKF.cpp:6-33) on the rows of X"""
+        q = self.model[3:7]
+        s = np.concatenate([np.zeros((len(X), 3)), np.broadcast_to(q, (len(X), 4)), X[:, :3],
+                            np.broadcast_to(self.gyro, (len(X), 3))], 1)
+        n = self.uwv.rk4(s, self.tau, dt)
+        v = X[:, :3] + (n[:, 7:10] - X[:, :3])
+        z = X[:, 3] + dt * qrot(q, v)[:, 2]
+        return np.concatenate([v, z[:, None]], 1)
+
+    def predict(self, dt):
+        self.mu, self.P = ukf_predict(self.lay, self.mu, self.P, lambda X: self.process(X, dt), dt * self.Q)
         self.model = self.uwv.rk4(self.model, self.tau, dt)
 
     def update_dvl(self, z, R):

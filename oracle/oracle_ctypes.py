@@ -286,15 +286,24 @@ class OracleVelBatch:
             if e:
                 raise RuntimeError("oracle vel predict failed: %s" % abi.STATUS.get(e, e))
 
-    def update_dvl(self, mu, cov):
-        mu = _f64(mu)
+    def update_dvl(self, mu, shared_cov=None, cov=None, mask=None):
+        """shared_cov 3x3 for the batch, or cov= [B][3][3] per instance; an
+        instance with mask[i] == 0 is not called."""
+        mu = _f64(mu).reshape(self.batch, 3)
+        R = _f64(shared_cov).reshape(1, 3, 3) if cov is None else _f64(cov).reshape(self.batch, 3, 3)
         for i in range(self.batch):
-            assert self.L.or_vel_update_dvl(self.ptr(i), dp(mu[i]), dp(cov)) == 0
+            if mask is not None and not mask[i]:
+                continue
+            assert self.L.or_vel_update_dvl(self.ptr(i), dp(mu[i]), dp(R[i if cov is not None else 0])) == 0
 
-    def update_pressure(self, mu, cov):
-        mu = _f64(mu)
+    def update_pressure(self, mu, shared_cov=None, cov=None, mask=None):
+        mu = _f64(mu).reshape(self.batch)
+        R = _f64(shared_cov).reshape(1) if cov is None else _f64(cov).reshape(self.batch)
         for i in range(self.batch):
-            assert self.L.or_vel_update_pressure(self.ptr(i), dp(mu[i:i + 1]), dp(np.array([cov]))) == 0
+            if mask is not None and not mask[i]:
+                continue
+            j = i if cov is not None else 0
+            assert self.L.or_vel_update_pressure(self.ptr(i), dp(mu[i:i + 1]), dp(R[j:j + 1])) == 0
 
     def get_state(self, model=False):
         x = np.empty((self.batch, 4))

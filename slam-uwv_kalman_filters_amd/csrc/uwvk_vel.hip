@@ -1070,6 +1070,15 @@ uwvk_status uwvk_vel_get_model_state(uwvk_vel* h, double* out) {
   return UWVK_OK;
 }
 
+uwvk_status uwvk_vel_get_status(uwvk_vel* h, uint32_t* status, int clear) {
+  UWVK_DEVICE_GUARD(h);
+  if (!h || !status) return UWVK_EINVAL;
+  HIPCHK(hipMemcpyAsync(status, h->d_status, (size_t)h->batch * 4, hipMemcpyDeviceToHost, h->stream));
+  if (clear) HIPCHK(hipMemsetAsync(h->d_status, 0, (size_t)h->batch * 4, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return UWVK_OK;
+}
+
 uwvk_status uwvk_vel_run_log(uwvk_vel* h, const uwvk_vel_log* log, int64_t first, int64_t count) {
   UWVK_DEVICE_GUARD(h);
   if (!h || !log || first < 0 || count < 0 || first + count > log->epochs) return UWVK_EINVAL;

@@ -31,7 +31,8 @@ SYMBOLS = [
     "uwvk_pose_ensemble_stats", "uwvk_pose_set_option", "uwvk_pose_timer_start", "uwvk_pose_timer_stop",
     "uwvk_vel_create", "uwvk_vel_destroy", "uwvk_vel_stream", "uwvk_vel_init", "uwvk_vel_setup_motion_model",
     "uwvk_vel_set_gyro", "uwvk_vel_set_efforts", "uwvk_vel_predict", "uwvk_vel_update_dvl",
-    "uwvk_vel_update_pressure", "uwvk_vel_get_state", "uwvk_vel_get_model_state", "uwvk_vel_run_log",
+    "uwvk_vel_update_pressure", "uwvk_vel_get_state", "uwvk_vel_get_model_state", "uwvk_vel_get_status",
+    "uwvk_vel_run_log",
     "uwvk_vel_set_option", "uwvk_vel_synchronize", "uwvk_vel_timer_start", "uwvk_vel_timer_stop",
     "uwvk_pose_ensemble_allreduce", "uwvk_comm_unique_id_bytes", "uwvk_comm_unique_id", "uwvk_comm_init",
     "uwvk_comm_destroy", "uwvk_comm_allreduce_sum_device", "uwvk_vel_set_process_noise",
@@ -87,6 +88,8 @@ def lib(path=None):
         L.uwvk_vel_stream.argtypes = [VP]
         L.uwvk_pose_destroy.argtypes = [VP]
         L.uwvk_vel_destroy.argtypes = [VP]
+        if hasattr(L, "uwvk_vel_get_status"):  # an older ABI-3 build (UWVK_LIB A/B runs) has no such getter
+            L.uwvk_vel_get_status.argtypes = [VP, VP, C.c_int]
         L.uwvk_comm_destroy.argtypes = [VP]
         L.uwvk_device_free.argtypes = [VP]
         L.uwvk_pose_tail_chunks.argtypes = [C.c_int64, C.c_int64, C.c_int64]
@@ -642,13 +645,27 @@ class VelocityUKFBatch:
     def predict(self, dt):
         _chk(self.L.uwvk_vel_predict(self.h, C.c_double(dt)), "vel_predict")
 
-    def update_dvl(self, mu, cov):
-        mu, cov = _f64(mu), _f64(cov)
-        _chk(self.L.uwvk_vel_update_dvl(self.h, _p(mu), None, _p(cov), None), "update_dvl")
+    def _update(self, fn, m, mu, shared, cov, mask, where):
+        mu = _f64(np.asarray(mu).reshape(self.batch, m))
+        shared = _f64(shared if shared is None else np.asarray(shared).reshape(m, m))
+        cov = _f64(cov if cov is None else np.asarray(cov).reshape(self.batch, m, m))
+        mask = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(self.batch), dtype=np.uint8)
+        _chk(fn(self.h, _p(mu), _p(cov), _p(shared), _p(mask)), where)
 
-    def update_pressure(self, mu, cov):
-        mu, cov = _f64(np.asarray(mu).reshape(-1)), _f64(np.atleast_1d(cov))
-        _chk(self.L.uwvk_vel_update_pressure(self.h, _p(mu), None, _p(cov), None), "update_pressure")
+    def update_dvl(self, mu, shared_cov=None, cov=None, mask=None):
+        """mu [B][3]; shared_cov 3x3 for the batch, or cov= [B][3][3] per
+        instance; mask= uint8 [B], 0 leaves that instance untouched."""
+        self._update(self.L.uwvk_vel_update_dvl, 3, mu, shared_cov, cov, mask, "update_dvl")
+
+    def update_pressure(self, mu, shared_cov=None, cov=None, mask=None):
+        """mu [B]; shared_cov scalar, or cov= [B][1][1] per instance; mask= as update_dvl."""
+        self._update(self.L.uwvk_vel_update_pressure, 1, mu, shared_cov, cov, mask, "update_pressure")
+
+    def get_status(self, clear=False):
+        """uint32 [B] status words (UWVK_ST_NOTPD is sticky); clear=True zeroes them after the read."""
+        out = np.zeros(self.batch, np.uint32)
+        _chk(self.L.uwvk_vel_get_status(self.h, _p(out), int(clear)), "vel_get_status")
+        return out
 
     def get_state(self, model=False):
         x = np.empty((self.batch, 4))
