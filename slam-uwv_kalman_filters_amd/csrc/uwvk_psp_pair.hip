@@ -21,6 +21,14 @@
 #ifndef PSP_PAIR_WAVES
 #define PSP_PAIR_WAVES 3
 #endif
+// the work-unit boundary (r09), each part switchable for A/Bs: the launch-wide
+// lane constants once per wave, the next unit's loads ahead of this unit's epilogue
+#ifndef PSP_PAIR_HOIST
+#define PSP_PAIR_HOIST 1
+#endif
+#ifndef PSP_PAIR_PREFETCH
+#define PSP_PAIR_PREFETCH 1
+#endif
 #include <algorithm>
 #include <atomic>
 
@@ -92,7 +100,7 @@ UWVK_DEV int pd_pidx(int e) {
 }
 UWVK_DEV constexpr int pd_diag53(int t) { return ((19 + t) * (20 + t)) / 2 + 19 + t; }
 // pd_pidx of every flat slot e = l + 32 t of a local lane, once per wave: the
-// map depends on the lane and the slot only, and load_pair / store_pair paid
+// map depends on the lane and the slot only, and a unit's load / store_pair paid
 // its sqrtf, fix-ups and products for 11 slots per lane in every work unit
 // (~750 VALU each).  16-bit entries (the largest index is 1,430) in LDS, one
 // table for both halves; the units' loads and stores read their 11 indices
@@ -110,20 +118,20 @@ UWVK_DEV void pd_tab_fill(unsigned short* tab, int l) {
 }
 
 // per-lane process-model constants of the 26-DOF layout (uwvk_psp_k.hip
-// lane_proc<26>), s = the local lane
-UWVK_DEV void lane_proc(const PoseBufs& b, const PoseShared& sh, int64_t inst, int s, ProcCtx& pc) {
+// lane_proc<26>), s = the local lane.  Everything here depends on the lane and
+// the launch's PoseShared only; the one per-instance value, the rho lane's
+// offset b.off[28 inst + 27], comes with the unit's loads (UnitIn::off_rho).
+UWVK_DEV void lane_proc(const PoseShared& sh, int s, ProcCtx& pc) {
   using L = Lay<26>;
   const uwvk_pose_parameter& P = sh.p;
   pc.vpart = s < 3 ? L::s_vel + s : ((s >= L::s_vel && s < L::s_vel + 3) ? L::s_acc + s - L::s_vel : -1);
   pc.nt_lane = 0.0;
   pc.off_lane = 0.0;
-  int k = -1;
   if (s >= L::s_bg && s < L::s_bg + 3) { pc.nt_lane = sh.ntau[0]; pc.off_lane = P.gyro_bias_offset[s - L::s_bg]; }
   if (s >= L::s_ba && s < L::s_ba + 3) { pc.nt_lane = sh.ntau[1]; pc.off_lane = P.acc_bias_offset[s - L::s_ba]; }
   if (s >= L::s_wv && s < L::s_wv + 4) pc.nt_lane = sh.ntau[5];
   if (s >= L::s_badcp && s < L::s_badcp + 2) pc.nt_lane = sh.ntau[6];
-  if (s == L::s_rho) { k = 27; pc.nt_lane = sh.ntau[7]; }
-  if (k >= 0) pc.off_lane = b.off[inst * 28 + k];
+  if (s == L::s_rho) pc.nt_lane = sh.ntau[7];
   pc.nt_tan = 0.0;
   if (s < 26 && scaled_dof(s)) pc.nt_tan = tan_ntau_sel<26>(s, sh);
 }
@@ -135,14 +143,14 @@ UWVK_DEV void lane_proc(const PoseBufs& b, const PoseShared& sh, int64_t inst, i
 // Only lane t touches entry t: no ordering with the other phases.
 struct ParLane {
   double q;    // dt^2 Q_ii (the PD table's entry 351 + t)
-  double off;  // the mean's offset
+  double off;  // the mean's offset (per instance: UnitIn::off_par)
   double nt;   // -1/tau of its block
 };
-UWVK_DEV ParLane par_lane(const PoseBufs& b, const PoseShared& sh, int64_t inst, int t) {
+// q and nt, the same for every unit of a launch
+UWVK_DEV ParLane par_lane(const PoseBufs& b, const PoseShared& sh, int t) {
   ParLane p{0.0, 0.0, 0.0};
   if (t < kPdN) {
     p.q = reinterpret_cast<const double2*>(b.Qp)[PG<26>::NP + t].y;
-    p.off = b.off[inst * 28 + t];
     p.nt = t < 9 ? sh.ntau[2] : (t < 18 ? sh.ntau[3] : sh.ntau[4]);
   }
   return p;
@@ -156,31 +164,68 @@ UWVK_DEV void par_epoch(double* px, int t, double dt, const ParLane& p) {
   }
 }
 
-// the pair's state through the 26-DOF layout: instance inst's Sigma~ subset,
-// 27 stored means, the parameters' diagonal and means (local lanes, 32 per instance)
-UWVK_DEV void load_pair(PspSmem<26>& sm, double* px, const unsigned short* tab, const PoseBufs& b, int64_t inst,
-                        int l) {
+// Everything a work unit reads from HBM before its first epoch, as registers:
+// the pair's state through the 26-DOF layout (PD: instance inst's Sigma~
+// subset, 27 stored means, the parameters' diagonal and means; PD = 0: a 26-DOF
+// handle's own packed triangle and mean; local lanes, 32 per instance), the
+// per-instance constants (stored rotation rate, the offsets of the rho lane and
+// of parameter l) and the first epoch's inputs, issued as one batch.  Every
+// load is under its lane's own mask (r09: a branch-free form in which every
+// lane loads a valid address and drops it measured 3% slower at 20 epochs,
+// profiles/EXPERIMENTS.md).  have = false (wave-uniform) issues no load and
+// defines every register as zero: the epilogue calls it for the next unit
+// whether there is one or not, so that nothing is live through the epochs.
+struct UnitIn {
+  double v[PG<26>::NSLOT];
+  double m, ps, pm;
+  double w[3];
+  double off_rho, off_par;
+  double g[3], a[3];
+  uint32_t fl;
+  bool have;
+};
+template <int PD>
+UWVK_DEV void unit_fetch(UnitIn& in, bool have, const unsigned short* tab, const PoseBufs& b, const EpochArgs& ea,
+                         int64_t unit, int64_t e0, bool imu, int h, int l) {
   using G = PG<26>;
-  const double* gs = b.sigma + inst * (int64_t)PG<53>::NP;
-  const double* gm = b.mu + inst * (int64_t)Lay<53>::store;
-  double v[G::NSLOT];
+  const int64_t inst = have ? 2 * unit + h : 0;
+  const double* gs = b.sigma + inst * (int64_t)(PD ? PG<53>::NP : G::NP);
+  const double* gm = b.mu + inst * (int64_t)(PD ? Lay<53>::store : Lay<26>::store);
+  in.have = have;
 #pragma unroll
   for (int t = 0; t < G::NSLOT; t++) {
     const int e = l + kLanes * t;
-    v[t] = e < G::NP ? gs[tab[e]] : 0.0;
+    in.v[t] = (have && e < G::NP) ? gs[PD ? (int)tab[e] : e] : 0.0;
   }
-  const double m = l < Lay<26>::store ? gm[pd_store(l)] : 0.0;
-  const bool pl = l < kPdN;
-  const double ps = pl ? gs[pd_diag53(l)] : 0.0, pm = pl ? gm[20 + l] : 0.0;
+  in.m = (have && l < Lay<26>::store) ? gm[PD ? pd_store(l) : l] : 0.0;
+  const bool pl = PD && have && l < kPdN;
+  in.ps = pl ? gs[pd_diag53(l)] : 0.0;
+  in.pm = pl ? gm[20 + l] : 0.0;
+  in.off_par = pl ? b.off[inst * 28 + l] : 0.0;
+  in.off_rho = (have && l == Lay<26>::s_rho) ? b.off[inst * 28 + 27] : 0.0;
+  in.fl = (have && imu) ? ea.flags[e0] : 0u;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    in.w[k] = have ? b.rot[inst * 3 + k] : 0.0;
+    in.g[k] = (have && imu) ? ea.gyro[(e0 * b.batch + inst) * 3 + k] : 0.0;
+    in.a[k] = (have && imu) ? ea.acc[(e0 * b.batch + inst) * 3 + k] : 0.0;
+  }
+}
+// the fetched state into the unit's LDS (after the previous unit's last LDS read)
+template <int PD>
+UWVK_DEV void unit_put(PspSmem<26>& sm, double* px, const UnitIn& in, int l) {
+  using G = PG<26>;
 #pragma unroll
   for (int t = 0; t < G::NSLOT; t++) {
     const int e = l + kLanes * t;
-    if (e < G::NP) sm.S[e] = v[t];
+    if (e < G::NP) sm.S[e] = in.v[t];
   }
-  if (l < Lay<26>::store) sm.mu[l] = m;
-  if (pl) {
-    px[l] = ps;
-    px[32 + l] = pm;
+  if (l < Lay<26>::store) sm.mu[l] = in.m;
+  if constexpr (PD) {
+    if (l < kPdN) {
+      px[l] = in.ps;
+      px[32 + l] = in.pm;
+    }
   }
   psync();
 }
@@ -209,26 +254,7 @@ UWVK_DEV void store_pair(const PspSmem<26>& sm, const double* px, const unsigned
 }
 
 // a 26-DOF handle's own state (PD = 0): the packed 26-DOF triangle and mean
-// (uwvk_psp_k.hip load_psp<26> / store_psp<26>, on 32 lanes per instance)
-UWVK_DEV void load_pair26(PspSmem<26>& sm, const PoseBufs& b, int64_t inst, int l) {
-  using G = PG<26>;
-  const double* gs = b.sigma + inst * (int64_t)G::NP;
-  const double* gm = b.mu + inst * (int64_t)Lay<26>::store;
-  double v[G::NSLOT];
-#pragma unroll
-  for (int t = 0; t < G::NSLOT; t++) {
-    const int e = l + kLanes * t;
-    v[t] = e < G::NP ? gs[e] : 0.0;
-  }
-  const double m = l < Lay<26>::store ? gm[l] : 0.0;
-#pragma unroll
-  for (int t = 0; t < G::NSLOT; t++) {
-    const int e = l + kLanes * t;
-    if (e < G::NP) sm.S[e] = v[t];
-  }
-  if (l < Lay<26>::store) sm.mu[l] = m;
-  psync();
-}
+// (uwvk_psp_k.hip store_psp<26>, on 32 lanes per instance)
 UWVK_DEV void store_pair26(const PspSmem<26>& sm, const PoseBufs& b, int64_t inst, int l) {
   using G = PG<26>;
   double* gs = b.sigma + inst * (int64_t)G::NP;
@@ -288,6 +314,25 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
   const uint32_t grid = gridDim.x;
   uint32_t u = blockIdx.x;
   if constexpr (PD) pd_tab_fill(pdx, olane());
+  // The lane's launch-wide constants, once per wave (PSP_PAIR_HOIST): they are
+  // live through every epoch anyway, so holding them across the units adds
+  // nothing at the register peak, and a unit's boundary no longer fetches
+  // them one load, wait and spill at a time.
+  auto lane_consts = [&](int l, ProcCtx& pc, ParLane& pl, LaneQ& lq) {
+    double dtv = ea.dt;
+    asm volatile("" : "+v"(dtv));
+    pc.dt = dtv;
+    pc.off = nullptr;
+    lane_proc(*b.shared, l, pc);
+    pl = PD ? par_lane(b, *b.shared, l) : ParLane{0.0, 0.0, 0.0};
+    lq = lane_q<26, 0>(b.Qp, l);
+  };
+  ProcCtx pc;
+  ParLane pl;
+  LaneQ lq;
+  if constexpr (PSP_PAIR_HOIST) lane_consts(olane(), pc, pl, lq);
+  UnitIn in;  // this unit's loads, or the next unit's issued in this one's epilogue
+  unit_fetch<PD>(in, false, pdx, b, ea, 0, 0, false, h, 0);
 #pragma unroll 1
   while (u < ea.units) {
     const PUnit tu = ticket_unit(ea, u);
@@ -297,6 +342,7 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
         __hip_atomic_store(ea.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // host-mapped word
       }
       u = grid + ticket_value(ea, ticket_issue(ea));
+      in.have = false;  // (a chunk unit is never prefetched)
       psync();
       continue;
     }
@@ -305,19 +351,16 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
     const int64_t e_begin = tu.e0, e_end = tu.e1;
     bool ok = true, nan = false;
     uint32_t cnt[4] = {0, 0, 0, 0};
-    ProcCtx pc;
-    for (int k = 0; k < 3; k++) pc.w[k] = b.rot[inst * 3 + k];
-    {
-      double dtv = ea.dt;
-      asm volatile("" : "+v"(dtv));
-      pc.dt = dtv;
-    }
-    pc.off = nullptr;
-    lane_proc(b, *b.shared, inst, l, pc);
-    const ParLane pl = PD ? par_lane(b, *b.shared, inst, l) : ParLane{0.0, 0.0, 0.0};
-    const LaneQ lq = lane_q<26, 0>(b.Qp, l);
-    uint32_t fl_n = 0;
-    double g_n[3] = {0, 0, 0}, a_n[3] = {0, 0, 0};
+    if constexpr (!PSP_PAIR_HOIST) lane_consts(l, pc, pl, lq);
+    // the unit's state, per-instance constants and first inputs: in registers
+    // already when the previous unit's epilogue issued them, else one batch now
+    // (a chunk unit's state is valid only after tail_wait's acquire)
+    if (!in.have) unit_fetch<PD>(in, true, pdx, b, ea, tu.unit, e_begin, e_end > e_begin, h, l);
+    for (int k = 0; k < 3; k++) pc.w[k] = in.w[k];
+    if (l == Lay<26>::s_rho) pc.off_lane = in.off_rho;
+    pl.off = in.off_par;
+    uint32_t fl_n = in.fl;
+    double g_n[3] = {in.g[0], in.g[1], in.g[2]}, a_n[3] = {in.a[0], in.a[1], in.a[2]};
     auto fetch = [&](int64_t e) {
       fl_n = ea.flags[e];
 #pragma unroll
@@ -326,9 +369,7 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
         a_n[k] = ea.acc[(e * B + inst) * 3 + k];
       }
     };
-    if (e_end > e_begin) fetch(e_begin);
-    if constexpr (PD) load_pair(sm, px, pdx, b, inst, l);
-    else load_pair26(sm, b, inst, l);
+    unit_put<PD>(sm, px, in, l);
     double ds = 1.0, ids = 1.0;  // time scale of the 26-DOF layout's Markov DOFs
     if (tu.chunk > 0) {
       const double2 c = reinterpret_cast<const double2*>(ea.tail_carry)[tu.tslot * 64 + lane_id()];
@@ -389,6 +430,17 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
         }
       }
     }
+    // The next unit (its ticket has long returned).  A whole pair unit has no
+    // predecessor to wait for, so everything it reads is loaded now, ahead of
+    // this unit's fold and scattered stores (k_psp_epoch_p's PspPre; the
+    // values go to LDS after store_pair has read it).  A chunk unit keeps the
+    // order above; a failing ticket issues no load.
+    const uint32_t un = grid + ticket_value(ea, vn);
+    {
+      const PUnit tx = ticket_unit(ea, un < ea.units ? un : 0u);
+      const bool have = PSP_PAIR_PREFETCH && un < ea.units && tx.chunk < 0;
+      unit_fetch<PD>(in, have, pdx, b, ea, tx.unit, tx.e0, tx.e1 > tx.e0, h, l);
+    }
     if (l == 0) {  // local lane 0 of each half: its instance's bookkeeping
       const uint32_t bits = (ok ? 0u : UWVK_ST_NOTPD) | (nan ? UWVK_ST_NAN : 0u);
       if (bits) __hip_atomic_fetch_or(b.status + inst, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -398,7 +450,6 @@ void k_psp_epoch_pair(PoseBufs b, PoseShared sh0, EpochArgs ea) {
       if (ea.accept_counts)
         for (int k = 0; k < 4; k++) ea.accept_counts[inst * 4 + k] += cnt[k];
     }
-    const uint32_t un = grid + ticket_value(ea, vn);
     const PUnit tn = ticket_unit(ea, u);  // re-derived: not kept live through the epochs
     const bool hand = tn.chunk >= 0 && tn.chunk + 1 < ea.chunks;
     if (hand) {  // hand on: Sigma~ and d unfolded (both halves' 64 lanes)
