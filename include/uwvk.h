@@ -76,7 +76,7 @@ typedef enum uwvk_status {
 /* per-instance status bits (the *_get_status getters of every filter family) */
 #define UWVK_ST_NOTPD 0x1u    /* Cholesky of Sigma failed (non-positive pivot) */
 #define UWVK_ST_NAN 0x2u      /* non-finite measurement skipped for this instance */
-#define UWVK_ST_NONFINITE 0x4u/* non-finite state after a step */
+#define UWVK_ST_NONFINITE 0x4u/* non-finite state after a step: RESERVED, no kernel raises it today (part of ABI 3) */
 /* UWVK_ST_SCHEDULE: engine fault, a tail-chunk hand-off timed out (see
  * UWVK_OPT_TAIL_SLOTS; never observed outside forced tests).  The instance's
  * state is then INVALID, not merely late: the chunks after the lost hand-off
@@ -341,7 +341,36 @@ uwvk_status uwvk_pose_reset_with_external_pose(uwvk_pose* h, const double* pose)
 uwvk_status uwvk_pose_get_state(uwvk_pose* h, double* x, double* P);
 /* getRotationRate (PoseUKF.cpp:693-699): batch*3 */
 uwvk_status uwvk_pose_get_rotation_rate(uwvk_pose* h, double* out);
-/* per-instance status words (UWVK_ST_*), batch uint32; clear = 1 resets them */
+/* Per-instance status words (UWVK_ST_*), batch uint32: waits for the handle's
+ * stream, copies the words and, if clear, zeroes the device words.  Both init
+ * calls zero them too (every instance becomes a new filter).  The bits are
+ * sticky until then.  NULL handle or status: UWVK_EINVAL.
+ *  - UWVK_ST_NAN: a non-finite measurement was skipped for that instance.
+ *  - UWVK_ST_NOTPD: a Cholesky factorisation of that instance's Sigma met a
+ *    non-positive pivot (negative, zero or NaN).  The call still returns
+ *    UWVK_OK.  The step is NOT skipped: the flagged instance's state and
+ *    covariance are overwritten and unspecified from then on (the full
+ *    BodyEfforts kernel even factors Sigma in place; in a run the later epochs
+ *    run on it as NaN); re-initialise the handle.  Every other instance,
+ *    the partner in a wave of the two-instances-per-wave kernel included, is
+ *    bitwise what it is beside a valid Sigma.
+ *    Which pivots are seen depends on the path.  The literal kernels
+ *    (UWVK_OPT_DENSE_SIGMA) and the CPU oracle factor all of Sigma at every
+ *    step and see every pivot.  A PSP step factors the leading k tangent DOFs
+ *    only and sees the first non-positive pivot p iff p < k:
+ *    predict 15; acceleration, velocity (DVL), water velocity (ADCP) 6;
+ *    pressure 19; BodyEfforts velocity-only 9; full BodyEfforts all of them;
+ *    XY, Z, geographic and delayed XY 0, i.e. never.  run_log sees what its
+ *    steps see, so a pivot below 15 at its first predict.  With p >= k the
+ *    step's formulas stay defined and its result is finite: an indefinite
+ *    Sigma whose leading 15 x 15 block is positive definite is not detected
+ *    on the PSP paths until a pressure or full BodyEfforts step reaches it.
+ *    A negative measurement variance is not screened (UWVK_ENAN is for
+ *    non-finite values only): where it leaves Sigma - C K^T indefinite the
+ *    update itself raises nothing, the next predict does (pivot < 15).
+ *    tests/test_gpu_pose_edges.py pins all of this.
+ *  - UWVK_ST_NONFINITE is reserved: no kernel raises it today.
+ *  - UWVK_ST_SCHEDULE: see above. */
 uwvk_status uwvk_pose_get_status(uwvk_pose* h, uint32_t* status, int clear);
 
 /* ---- device-resident measurement log (persistent multi-epoch path) ----- */

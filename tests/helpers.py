@@ -53,3 +53,16 @@ def qrot_inv(q, v):
     w, u = q[..., :1], -q[..., 1:]
     t = 2.0 * np.cross(u, v)
     return v + w * t + np.cross(u, t)
+
+
+def pivots(P):
+    """pivots of the unpivoted LDL^T of P, up to and including the first
+    non-positive one (the signs a kernel's Cholesky meets)"""
+    A = np.array(P, float)
+    d = []
+    for k in range(len(A)):
+        d.append(A[k, k])
+        if not A[k, k] > 0:
+            break
+        A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k, k + 1:]) / A[k, k]
+    return np.array(d)

@@ -25,7 +25,7 @@ import pytest
 import oracle_ctypes as O
 import small_scenes as S
 import visual_scene as V
-from helpers import cov_err, pose_setup, state_err
+from helpers import cov_err, pivots, pose_setup, state_err
 from uwvk import abi, engine, synth
 from uwvk.small import BottomUKFBatch, IndirectPoseUKFBatch
 
@@ -38,18 +38,6 @@ def same(a, b, rows=slice(None)):
     """(x, P) pairs bitwise equal on `rows`"""
     np.testing.assert_array_equal(a[0][rows], b[0][rows])
     np.testing.assert_array_equal(a[1][rows], b[1][rows])
-
-
-def pivots(P):
-    """pivots of the unpivoted LDL^T of P (the signs the kernel's Cholesky meets)"""
-    A = np.array(P, float)
-    d = []
-    for k in range(len(A)):
-        d.append(A[k, k])
-        if not A[k, k] > 0:
-            break
-        A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k, k + 1:]) / A[k, k]
-    return np.array(d)
 
 
 def masks(B, off):

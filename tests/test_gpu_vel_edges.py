@@ -30,7 +30,7 @@ import pytest
 
 import oracle_ctypes as O
 import vel_scenes as VS
-from helpers import cov_err
+from helpers import cov_err, pivots
 from uwvk import engine, synth
 
 pytestmark = pytest.mark.gpu
@@ -96,18 +96,6 @@ def close(got, ref, tol, what=""):
     es, ec, em = errors(got, ref)
     print("%s state %.3g cov %.3g model %.3g" % (what, es, ec, em))
     assert es < tol and ec < tol and em < TOL_MODEL, (what, es, ec, em)
-
-
-def pivots(P):
-    """pivots of the unpivoted LDL^T of P (the signs v_chol meets)"""
-    A = np.array(P, float)
-    d = []
-    for k in range(len(A)):
-        d.append(A[k, k])
-        if not A[k, k] > 0:
-            break
-        A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k, k + 1:]) / A[k, k]
-    return np.array(d)
 
 
 # ---- 1. scenes against the oracle -----------------------------------------
