@@ -56,7 +56,8 @@ extern "C" {
  *      uwvk_schedule_fixes; uwvk_pose_delayed, uwvk_pose_run_log_delayed,
  *      uwvk_schedule_delayed; uwvk_bottom_log, uwvk_bottom_track, UWVK_BEV_*,
  *      uwvk_bottom_log_check, uwvk_bottom_run_log, uwvk_bottom_synchronize;
- *      uwvk_vel_get_status. */
+ *      uwvk_vel_get_status; uwvk_ipose_log, uwvk_ipose_track,
+ *      uwvk_ipose_log_check, uwvk_ipose_run_log, uwvk_ipose_synchronize. */
 #define UWVK_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
@@ -1008,6 +1009,100 @@ uwvk_status uwvk_ipose_update_visual(uwvk_ipose* h, int32_t n_features, const do
 uwvk_status uwvk_ipose_get_corrected_pose(uwvk_ipose* h, double* out);
 uwvk_status uwvk_ipose_get_state(uwvk_ipose* h, double* x, double* P);
 uwvk_status uwvk_ipose_get_status(uwvk_ipose* h, uint32_t* status, int clear);
+
+/* ---- IndirectPoseUKF in a run: a device-resident multi-epoch log --------- */
+/* One epoch is updatePoseReference, predictionStep(dt), then zero or more
+ * marker observations (integrateMeasurement), in this order.  One launch covers
+ * up to 4096 epochs with (mu, Sigma) resident in LDS. */
+typedef struct uwvk_ipose_log {
+  int64_t epochs;
+  double dt;                       /* predict step (host value), > 0; unused if dt_epoch is given */
+  const double* dt_epoch;          /* HOST [epochs] predict step of each epoch, each > 0; NULL = dt for all */
+  const double* pose_ref;          /* DEVICE [epochs][batch][7] (updatePoseReference of that epoch);
+                                      NULL = the handle's reference stays what it is */
+  const int64_t* visual_offset;    /* HOST [epochs + 1], non-decreasing (CSR): epoch e integrates the visual
+                                      rows visual_offset[e] .. visual_offset[e+1]-1 in that order;
+                                      NULL only if n_visual == 0 */
+  int64_t n_visual;                /* visual rows */
+  int32_t n_features;              /* features of every row, >= 1 if a row is used */
+  const double* features;          /* DEVICE [n_visual][batch][n_features][2] */
+  const double* feature_cov;       /* DEVICE [n_visual][batch][n_features][4], NULL = shared_feature_cov */
+  const double* shared_feature_cov;/* HOST [n_features][4], serves every row */
+  const double* feature_positions; /* HOST [n_features][3] */
+  const double* marker_pose;       /* DEVICE [n_visual][batch][7], NULL = shared_marker_pose */
+  const double* shared_marker_pose;/* HOST [n_visual][7], one per row */
+  double cov_marker_pose[36];      /* host, shared */
+  double camera[4];                /* host, shared: fx, fy, cx, cy */
+  double camera_in_body[7];        /* host, shared */
+} uwvk_ipose_log;
+
+typedef struct uwvk_ipose_track {
+  int64_t every, capacity;         /* as uwvk_bottom_track */
+  double* mean;                    /* DEVICE [records][batch][7], nullable */
+  double* variance;                /* DEVICE [records][batch][6] diagonal of Sigma, nullable */
+  double* corrected;               /* DEVICE [records][batch][7] pose_ref * pose_error at that epoch, in
+                                      uwvk_ipose_get_corrected_pose's layout, nullable */
+} uwvk_ipose_track;
+
+/* host only, no device needed: the checks uwvk_ipose_run_log makes before it
+ * queues anything, over epochs [first, first + count) and their visual rows.
+ * UWVK_EINVAL: log NULL; a negative range or one past log->epochs; n_visual < 0,
+ * or visual_offset NULL while n_visual != 0; the predict step of an epoch of
+ * the range (dt_epoch's entry, or dt if dt_epoch is NULL) not > 0, a NaN
+ * included; a visual_offset entry of the range that is negative, above n_visual
+ * or below its predecessor; and, if the range holds a visual row: n_features
+ * < 1; features or feature_positions NULL; feature_cov and shared_feature_cov
+ * both NULL; marker_pose and shared_marker_pose both NULL.
+ * UWVK_ENAN: a non-finite value among the host inputs the range uses: the
+ * predict steps and, if it holds a visual row, shared_feature_cov (when
+ * feature_cov is NULL), feature_positions, the range's rows of
+ * shared_marker_pose (when marker_pose is NULL), cov_marker_pose, camera,
+ * camera_in_body. */
+uwvk_status uwvk_ipose_log_check(const uwvk_ipose_log* log, int64_t first, int64_t count);
+
+/* Epochs [first, first + count) of the log.  Epoch e: pose_ref[e] becomes the
+ * handle's reference; predict with that epoch's step; one visual update per row
+ * of the epoch, in row order; a track record if e is a record epoch (numbered
+ * as uwvk_pose_track_records numbers them; a record does not end a launch).
+ * The handle's UWVK_OPT_SO3_RIGHT, process noise and tau apply.  Afterwards the
+ * handle's pose reference is that of the last epoch (per instance: its last
+ * finite one), as after the single calls.
+ *
+ * The result is bitwise that of the single calls on the same handle state in
+ * this order (uwvk_ipose_set_pose_reference, uwvk_ipose_predict, one
+ * uwvk_ipose_update_visual per row): mu, Sigma, the status words, and every
+ * mean / variance record against uwvk_ipose_get_state at that epoch.  Calls
+ * over adjacent ranges give bitwise what one call over the whole range gives.
+ * The corrected records are computed on the device and agree with
+ * uwvk_ipose_get_corrected_pose (host arithmetic) to rounding, not bitwise.
+ *
+ * The payloads are in device memory, so what the single calls refuse on the
+ * host is handled per instance here:
+ *  - a non-finite feature, feature covariance or per-instance marker pose of an
+ *    instance at a row: that row is skipped for that instance (the single call
+ *    with the instance masked out), UWVK_ST_NAN;
+ *  - a non-finite pose_ref of an instance at an epoch: the instance keeps its
+ *    last finite reference (so does the handle's stored one), UWVK_ST_NAN; its
+ *    predict still runs, which does not read the reference;
+ *  - a predict whose Cholesky meets a non-positive pivot: (mu, Sigma) stays as
+ *    before it, UWVK_ST_NOTPD, and the run carries on;
+ *  - a visual row in which any feature's update fails (at the sigma spread or
+ *    in apply_delta's re-spread) is discarded for that instance as a whole, as
+ *    by uwvk_ipose_update_visual: (mu, Sigma) as before the row,
+ *    UWVK_ST_NOTPD, later rows and epochs still run.
+ * applied (DEVICE [batch], nullable, zeroed by the caller): the visual rows
+ * that changed the instance are added to it.
+ *
+ * Returns uwvk_ipose_log_check's result first, then UWVK_EINVAL for a track
+ * with every <= 0, all three buffers NULL or capacity <
+ * uwvk_pose_track_records(first, count, every), then UWVK_ENOTINIT before
+ * uwvk_ipose_init, all with nothing queued and the state untouched.
+ * Asynchronous on the handle's stream like uwvk_bottom_run_log: the host arrays
+ * are copied before it returns; the getters and uwvk_ipose_synchronize wait. */
+uwvk_status uwvk_ipose_run_log(uwvk_ipose* h, const uwvk_ipose_log* log, int64_t first, int64_t count,
+                               uint32_t* applied /* DEVICE [batch] visual rows applied; nullable, caller zeroes */,
+                               const uwvk_ipose_track* track /* nullable */);
+uwvk_status uwvk_ipose_synchronize(uwvk_ipose* h);
 
 #ifdef __cplusplus
 }

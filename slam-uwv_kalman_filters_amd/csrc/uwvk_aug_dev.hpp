@@ -133,11 +133,15 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 // ---------------------------------------------------------------------------
 // Engine<M>: per-instance LDS layout and the group-cooperative UKF steps.
 // Every member is called by ALL threads of the block (they contain barriers).
+// LANES (a power of two >= N) widens the group beyond the smallest that holds
+// the N sigma points: the lanes g >= N take every barrier and write nothing, so
+// an engine can share a block with a wider one (k_ipose_run).
 // ---------------------------------------------------------------------------
-template <class M>
+template <class M, int LANES = 0>
 struct Engine {
   static constexpr int n = M::dof, S = M::store, N = 2 * n + 1;
-  static constexpr int G = pow2_at_least(N);
+  static constexpr int G = LANES ? LANES : pow2_at_least(N);
+  static_assert(G >= N && (G & (G - 1)) == 0, "a lane group holds one sigma point per lane");
   static constexpr int IPB = G >= 64 ? 1 : 64 / G;
   static constexpr int BLOCK = G >= 64 ? G : 64;
   // per-instance LDS words (doubles)

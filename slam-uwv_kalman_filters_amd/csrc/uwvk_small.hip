@@ -312,14 +312,14 @@ __global__ __launch_bounds__(BE::BLOCK) void k_bottom_run(SmallBufs b, BottomRun
 }
 
 // ---- IndirectPoseUKF -------------------------------------------------------
-// predictionStepImpl (IndirectPoseUKF.cpp:80-92) + processModel (:7-20)
-template <int SR>
-__global__ __launch_bounds__(IE<SR>::BLOCK) void k_ipose_predict(SmallBufs b, M36 Q, double tau, double dt) {
-  using E = IE<SR>;
-  __shared__ double smem[E::IPB * E::words];
-  int64_t inst;
-  E e = make_engine<E>(smem, b, nullptr, &inst);
-  load(e, b, inst);
+// The step bodies, on an engine whose (mu, Sigma) is in LDS.  The single kernels
+// and k_ipose_run both call them, so both compile the same expressions: the
+// run's bitwise contract (include/uwvk.h) rests on that, as for BottomUKF.
+
+// predictionStepImpl (IndirectPoseUKF.cpp:80-92) + processModel (:7-20); E is
+// the 6-DOF engine at either lane count
+template <int SR, class E>
+UWVK_DEV bool ipose_predict_step(E& e, const M36& Q, double tau, double dt) {
   // Q' = dt^2 (Q with the orientation block R (2/(tau dt) Q_o) R^T), R = mu's rotation
   double Rm[9];
   {
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(IE<SR>::BLOCK) void k_ipose_predict(SmallBufs b, M3
     return dt2 * t;
   };
   const double ntau = -1.0 / tau;
-  const bool ok = e.predict(
+  return e.predict(
       [&](double* x) {
         double l[3], d[3], ex[4], r[4];
         so3_log(x + 3, l);
@@ -359,35 +359,208 @@ __global__ __launch_bounds__(IE<SR>::BLOCK) void k_ipose_predict(SmallBufs b, M3
         for (int k = 0; k < 4; k++) x[3 + k] = r[k];
       },
       qf);
-  store(e, b, inst, ok);
 }
 
 // integrateMeasurement(marker features, ...) (IndirectPoseUKF.cpp:94-135):
-// augment with the marker pose, one S2 update per feature, keep the filter block
+// augment with the marker pose, one S2 update per feature (visual_loop), keep
+// the filter block.  This instance's 36 / 7 / 7 words start at sigma[at * 36],
+// mu[at * 7] and marker[mat], in HBM (the single kernel) or LDS (the run); they
+// are read or written only if `take`.
+template <class E>
+UWVK_DEV void ipose_augment(E& e, bool take, const double* sigma, const double* mu, int64_t at,
+                            const double* cov_marker, const double* marker, int64_t mat) {
+  if (take) {
+    for (int i = e.g; i < 144; i += E::G) {
+      const int r = i / 12, c = i % 12;
+      double v = 0.0;
+      if (r < 6 && c < 6) v = sigma[at * 36 + r * 6 + c];
+      else if (r >= 6 && c >= 6) v = cov_marker[(r - 6) * 6 + (c - 6)];
+      e.sm[E::o_sig + i] = v;
+    }
+    for (int k = e.g; k < 14; k += E::G) e.sm[E::o_mu + k] = k < 7 ? mu[at * 7 + k] : marker[mat + (k - 7)];
+  }
+  __syncthreads();
+}
+template <class E>
+UWVK_DEV void ipose_extract(E& e, bool take, double* sigma, double* mu, int64_t at) {
+  if (take) {
+    for (int i = e.g; i < 36; i += E::G) sigma[at * 36 + i] = e.sm[E::o_sig + (i / 6) * 12 + (i % 6)];
+    for (int k = e.g; k < 7; k += E::G) mu[at * 7 + k] = e.sm[E::o_mu + k];
+  }
+}
+
+template <int SR>
+__global__ __launch_bounds__(IE<SR>::BLOCK) void k_ipose_predict(SmallBufs b, M36 Q, double tau, double dt) {
+  using E = IE<SR>;
+  __shared__ double smem[E::IPB * E::words];
+  int64_t inst;
+  E e = make_engine<E>(smem, b, nullptr, &inst);
+  load(e, b, inst);
+  const bool ok = ipose_predict_step<SR>(e, Q, tau, dt);
+  store(e, b, inst, ok);
+}
+
 template <int SR>
 __global__ __launch_bounds__(IAE<SR>::BLOCK) void k_ipose_visual(SmallBufs b, VisArgs va) {
   using E = IAE<SR>;
   __shared__ double smem[E::IPB * E::words];
   int64_t inst;
   E e = make_engine<E>(smem, b, va.mask, &inst);
-  if (e.live) {
-    for (int i = e.g; i < 144; i += E::G) {
-      const int r = i / 12, c = i % 12;
-      double v = 0.0;
-      if (r < 6 && c < 6) v = b.sigma[inst * 36 + r * 6 + c];
-      else if (r >= 6 && c >= 6) v = va.cov_marker[(r - 6) * 6 + (c - 6)];
-      e.sm[E::o_sig + i] = v;
-    }
-    for (int k = e.g; k < 14; k += E::G)
-      e.sm[E::o_mu + k] = k < 7 ? b.mu[inst * 7 + k] : va.marker[inst * va.marker_stride + (k - 7)];
-  }
-  __syncthreads();
+  ipose_augment(e, e.live, b.sigma, b.mu, inst, va.cov_marker, va.marker, inst * va.marker_stride);
   const bool ok = visual_loop<E, 7, true>(e, va, inst);
-  if (e.live && ok) {
-    for (int i = e.g; i < 36; i += E::G) b.sigma[inst * 36 + i] = e.sm[E::o_sig + (i / 6) * 12 + (i % 6)];
-    for (int k = e.g; k < 7; k += E::G) b.mu[inst * 7 + k] = e.sm[E::o_mu + k];
-  }
+  ipose_extract(e, e.live && ok, b.sigma, b.mu, inst);
   if (e.live && !ok && e.g == 0) b.status[inst] |= UWVK_ST_NOTPD;
+}
+
+// getCorrectedPose (IndirectPoseUKF.cpp:137-142): o = r * e, pose_ref * pose_error,
+// each t(3) q(4): t = t_ref + R_ref p_err (Eigen _transformVector), q = q_ref * q_err
+__host__ __device__ inline void ipose_corrected(const double* r, const double* e, double* o) {
+  const double* q = r + 3;
+  double uv[3] = {2 * (q[2] * e[2] - q[3] * e[1]), 2 * (q[3] * e[0] - q[1] * e[2]), 2 * (q[1] * e[1] - q[2] * e[0])};
+  double t2[3] = {q[2] * uv[2] - q[3] * uv[1], q[3] * uv[0] - q[1] * uv[2], q[1] * uv[1] - q[2] * uv[0]};
+  for (int k = 0; k < 3; k++) o[k] = r[k] + (e[k] + q[0] * uv[k] + t2[k]);
+  const double* b = e + 3;
+  o[3] = q[0] * b[0] - q[1] * b[1] - q[2] * b[2] - q[3] * b[3];
+  o[4] = q[0] * b[1] + q[1] * b[0] + q[2] * b[3] - q[3] * b[2];
+  o[5] = q[0] * b[2] + q[2] * b[0] + q[3] * b[1] - q[1] * b[3];
+  o[6] = q[0] * b[3] + q[3] * b[0] + q[1] * b[2] - q[2] * b[1];
+}
+
+// ---- IndirectPoseUKF in a run (uwvk_ipose_run_log) ---------------------------
+// One launch covers up to kIPoseChunk epochs.  A 64-lane block holds two
+// instances of 32 lanes, the visual engine's shape; the predict runs on the
+// 6-DOF engine widened to the same 32 lanes (its lanes >= 13 idle).  The home of
+// (mu, Sigma 6x6) is the 6-DOF engine's LDS words: loaded once, stored once.  A
+// visual row copies it into the augmented engine's own words and copies the
+// filter block back only if every feature's update succeeded, so a failed row
+// leaves the home untouched.  The pose reference is not copied: each instance
+// keeps a pointer to its last finite one (a row of the log, or the handle's),
+// which visual_loop reads as the single kernel does, and stores it at exit.
+// Barriers are uniform as in k_bottom_run: the epoch table is uniform over the
+// grid and a skip is the engine's `live` flag of that step.
+constexpr int64_t kIPoseChunk = kBottomChunk;
+template <int SR>
+using IE32 = Engine<IPoseM<SR>, IAE<SR>::G>;
+struct IPoseEpoch {  // one row of the device epoch table
+  double dt;
+  int64_t row;       // first visual row of this epoch
+  int32_t rows;      // visual rows of this epoch
+  int32_t record;    // track record of this call after this epoch, -1: none
+};
+struct IPoseRunArgs {
+  const IPoseEpoch* ev;     // DEVICE [count], this launch's epochs
+  int32_t count;
+  const double* pose_ref;   // this launch's first epoch: [count][batch][7], nullable
+  double* ref_io;           // the handle's pose_ref [batch][7]: read at entry, written at exit
+  const double* marker_rows;// DEVICE shared marker poses [rows of this call][7], or NULL (per instance)
+  int64_t row_base;         // the visual row that marker_rows starts at
+  uint32_t* applied;        // [batch], nullable
+  double* tr_mean;          // [records][batch][7], nullable
+  double* tr_var;           // [records][batch][6], nullable
+  double* tr_corr;          // [records][batch][7], nullable
+  double tau;
+  M36 Q;
+  VisArgs va;               // features, fcov, marker: row 0 of the log's arrays; ref, mask unused
+};
+
+// true in every lane of a 32-lane group if `bad` is in any of them
+UWVK_DEV bool group32_any(bool bad) { return (uint32_t)(__ballot(bad) >> (threadIdx.x & 32)) != 0u; }
+
+template <int SR>
+__global__ __launch_bounds__(IAE<SR>::BLOCK) void k_ipose_run(SmallBufs b, IPoseRunArgs a) {
+  using EP = IE32<SR>;
+  using EV = IAE<SR>;
+  static_assert(EP::G == EV::G && EP::IPB == EV::IPB && EP::BLOCK == EV::BLOCK, "one lane group for both engines");
+  constexpr int kWords = EP::words + EV::words;
+  __shared__ double smem[EV::IPB * kWords];
+  const int gi = threadIdx.x / EV::G, g = threadIdx.x % EV::G;
+  const int64_t inst = (int64_t)blockIdx.x * EV::IPB + gi;
+  const bool in = inst < b.batch;
+  EP ep;
+  EV ev;
+  ep.g = ev.g = g;
+  ep.sm = smem + gi * kWords;
+  ev.sm = ep.sm + EP::words;
+  double* const sig = ep.sm + EP::o_sig;  // the home of (mu, Sigma)
+  double* const mu = ep.sm + EP::o_mu;
+  if (!in) {  // the empty slot of the last block: valid states, so its (unused) steps converge at once
+    for (int i = g; i < 36; i += EP::G) sig[i] = i % 7 == 0 ? 1.0 : 0.0;
+    for (int k = g; k < 7; k += EP::G) mu[k] = k == 3 ? 1.0 : 0.0;
+    for (int i = g; i < 144; i += EV::G) ev.sm[EV::o_sig + i] = i % 13 == 0 ? 1.0 : 0.0;
+    for (int k = g; k < 14; k += EV::G) ev.sm[EV::o_mu + k] = k == 3 || k == 10 ? 1.0 : 0.0;
+  }
+  ep.live = in;
+  load(ep, b, inst);
+  const double* ref = a.ref_io + inst * 7;  // dereferenced only if `in`
+  const double* const ref_in = ref;
+  uint32_t st = 0, n_applied = 0;
+  for (int32_t t = 0; t < a.count; t++) {
+    const IPoseEpoch epoch = a.ev[t];
+    // updatePoseReference: a non-finite one leaves the instance on its last finite reference
+    if (a.pose_ref) {  // uniform
+      const double* cand = a.pose_ref + ((int64_t)t * b.batch + inst) * 7;
+      const bool bad = group32_any(in && g < 7 && !finite_dev(cand[g]));
+      if (in && !bad) ref = cand;
+      if (bad) st |= UWVK_ST_NAN;
+    }
+    // predictionStep; it does not read the reference
+    ep.live = in;
+    if (!ipose_predict_step<SR>(ep, a.Q, a.tau, epoch.dt) && in) st |= UWVK_ST_NOTPD;
+    // the marker observations of this epoch, in row order
+    for (int32_t r = 0; r < epoch.rows; r++) {  // uniform
+      const int64_t row = epoch.row + r;
+      VisArgs vr = a.va;
+      vr.features = a.va.features + row * b.batch * vr.nf * 2;
+      if (vr.fcov_stride) vr.fcov = a.va.fcov + row * b.batch * vr.fcov_stride;
+      vr.marker = vr.marker_stride ? a.va.marker + row * b.batch * 7 : a.marker_rows + (row - a.row_base) * 7;
+      vr.ref = ref - inst * 7;  // visual_loop reads ref[inst * 7 + k]
+      bool bad = false;
+      if (in) {  // what the single call refuses on the host (stage_visual), per instance
+        const double* f = vr.features + inst * vr.nf * 2;
+        for (int i = g; i < vr.nf * 2; i += EV::G) bad |= !finite_dev(f[i]);
+        if (vr.fcov_stride) {
+          const double* c = vr.fcov + inst * vr.fcov_stride;
+          for (int i = g; i < vr.nf * 4; i += EV::G) bad |= !finite_dev(c[i]);
+        }
+        if (vr.marker_stride && g < 7) bad |= !finite_dev(vr.marker[inst * 7 + g]);
+      }
+      bad = group32_any(bad);
+      if (bad) st |= UWVK_ST_NAN;
+      ev.live = in && !bad;
+      ipose_augment(ev, in, sig, mu, 0, a.va.cov_marker, vr.marker, inst * vr.marker_stride);
+      const bool ok = visual_loop<EV, 7, true>(ev, vr, inst);
+      ipose_extract(ev, ev.live && ok, sig, mu, 0);
+      if (ev.live && ok) n_applied++;
+      if (ev.live && !ok) st |= UWVK_ST_NOTPD;
+      __syncthreads();
+    }
+    // track record, straight from LDS (every step above ends in a barrier)
+    if (epoch.record >= 0 && in) {
+      const int64_t at = (int64_t)epoch.record * b.batch + inst;
+      if (a.tr_mean && g < 7) a.tr_mean[at * 7 + g] = mu[g];
+      if (a.tr_var && g < 6) a.tr_var[at * 6 + g] = sig[g * 6 + g];
+      if (a.tr_corr && g == 7) {
+        double rr[7], ee[7], oo[7];
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+          rr[k] = ref[k];
+          ee[k] = mu[k];
+        }
+        ipose_corrected(rr, ee, oo);
+#pragma unroll
+        for (int k = 0; k < 7; k++) a.tr_corr[at * 7 + k] = oo[k];
+      }
+    }
+  }
+  ep.live = in;
+  store(ep, b, inst, true);
+  if (in) {
+    if (ref != ref_in && g < 7) a.ref_io[inst * 7 + g] = ref[g];
+    if (g == 0) {
+      if (st) b.status[inst] |= st;
+      if (a.applied) a.applied[inst] += n_applied;
+    }
+  }
 }
 
 int64_t grid_of(int64_t batch, int ipb) { return (batch + ipb - 1) / ipb; }
@@ -410,56 +583,53 @@ struct SmallHandle {
   SmallBufs bufs() const { return SmallBufs{batch, d_mu, d_sigma, d_status}; }
 };
 
-// The epoch table of one uwvk_bottom_run_log call: written into pinned host
-// memory before the call returns, copied to the device on the handle's stream.
-// A slot is free again once the event behind its last launch has passed.
-struct BottomStage {
-  BottomEpoch* host = nullptr;  // pinned
-  BottomEpoch* dev = nullptr;
-  int64_t cap = 0;              // epochs
+// The host arrays of one uwvk_bottom_run_log / uwvk_ipose_run_log call (the
+// epoch table; for IndirectPoseUKF the shared visual inputs before it): written
+// into pinned host memory before the call returns, copied to the device on the
+// handle's stream.  A slot is free again once the event behind its last launch
+// has passed.
+struct StageSlot {
+  char* host = nullptr;  // pinned
+  char* dev = nullptr;
+  size_t cap = 0;        // bytes
   hipEvent_t done = nullptr;
   bool used = false;
 };
 
-struct uwvk_bottom : SmallHandle {
-  M9 Q{};
-  std::vector<BottomStage> stages;
-};
-
-static void bottom_release_stages(uwvk_bottom* h) {
-  for (BottomStage& s : h->stages) {
+static void stage_release(std::vector<StageSlot>& stages) {
+  for (StageSlot& s : stages) {
     if (s.host) (void)hipHostFree(s.host);
     if (s.dev) (void)hipFree(s.dev);
     if (s.done) (void)hipEventDestroy(s.done);
   }
-  h->stages.clear();
+  stages.clear();
 }
 
-// a slot of at least `epochs` rows that no queued launch reads any more
-static BottomStage* bottom_stage(uwvk_bottom* h, int64_t epochs) {
-  BottomStage* s = nullptr;
-  for (BottomStage& c : h->stages)
+// a slot of at least `bytes` that no queued launch reads any more
+static StageSlot* stage_acquire(std::vector<StageSlot>& stages, size_t bytes) {
+  StageSlot* s = nullptr;
+  for (StageSlot& c : stages)
     if (!c.used || hipEventQuery(c.done) == hipSuccess) {
       c.used = false;
       if (!s) s = &c;
     }
   if (!s) {
-    h->stages.emplace_back();
-    s = &h->stages.back();
+    stages.emplace_back();
+    s = &stages.back();
     if (hipEventCreateWithFlags(&s->done, hipEventDisableTiming) != hipSuccess) {
       s->done = nullptr;
-      h->stages.pop_back();
+      stages.pop_back();
       return nullptr;
     }
   }
-  if (s->cap < epochs) {
+  if (s->cap < bytes) {
     if (s->host) (void)hipHostFree(s->host);
     if (s->dev) (void)hipFree(s->dev);
     s->host = s->dev = nullptr;
     s->cap = 0;
-    const int64_t cap = std::max<int64_t>(epochs, 1024);
-    if (hipHostMalloc((void**)&s->host, (size_t)cap * sizeof(BottomEpoch), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void**)&s->dev, (size_t)cap * sizeof(BottomEpoch)) != hipSuccess) {
+    const size_t cap = std::max<size_t>(bytes, 32768);
+    if (hipHostMalloc((void**)&s->host, cap, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void**)&s->dev, cap) != hipSuccess) {
       if (s->host) (void)hipHostFree(s->host);
       s->host = s->dev = nullptr;
       return nullptr;
@@ -468,10 +638,17 @@ static BottomStage* bottom_stage(uwvk_bottom* h, int64_t epochs) {
   }
   return s;
 }
+
+struct uwvk_bottom : SmallHandle {
+  M9 Q{};
+  std::vector<StageSlot> stages;
+};
+
 struct uwvk_ipose : SmallHandle {
   M36 Q{};
   double tau = 1.0;
   int so3_right = 1;  // UWVK_OPT_SO3_RIGHT (uwvk_ipose_set_option), default body frame
+  std::vector<StageSlot> stages;
 };
 
 static void small_destroy(SmallHandle* h) {
@@ -554,7 +731,7 @@ void uwvk_bottom_destroy(uwvk_bottom* h) {
   UWVK_DEVICE_GUARD(h);
   if (!h) return;
   small_destroy(h);  // waits for the stream first
-  bottom_release_stages(h);
+  stage_release(h->stages);
   delete h;
 }
 
@@ -709,13 +886,14 @@ uwvk_status uwvk_bottom_run_log(uwvk_bottom* h, const uwvk_bottom_log* log, int6
     return UWVK_EINVAL;
   if (!h->has_state) return UWVK_ENOTINIT;
   if (count == 0) return UWVK_OK;
-  BottomStage* sg = bottom_stage(h, count);
+  StageSlot* sg = stage_acquire(h->stages, (size_t)count * sizeof(BottomEpoch));
   if (!sg) return UWVK_ENOMEM;
+  BottomEpoch* const table = (BottomEpoch*)sg->host;
   const uint32_t beam_bits = (1u << log->beams) - 1u;
   int32_t record = 0;
   for (int64_t k = 0; k < count; k++) {
     const int64_t e = first + k;
-    BottomEpoch& ev = sg->host[k];
+    BottomEpoch& ev = table[k];
     ev.flags = log->flags[e];
     ev.range_row = (ev.flags & beam_bits) ? log->range_index[e] : 0;
     ev.normal_row = (ev.flags & UWVK_BEV_NORMAL) ? log->normal_index[e] : 0;
@@ -748,7 +926,7 @@ uwvk_status uwvk_bottom_run_log(uwvk_bottom* h, const uwvk_bottom_log* log, int6
   // one launch per chunk of epochs; the state's round trip through HBM is exact
   uwvk_status st = UWVK_OK;
   for (int64_t k = 0; k < count && st == UWVK_OK; k += kBottomChunk) {
-    a.ev = sg->dev + k;
+    a.ev = (const BottomEpoch*)sg->dev + k;
     a.count = (int32_t)std::min<int64_t>(kBottomChunk, count - k);
     a.velocity = log->velocity + (first + k) * h->batch * 3;
     hipLaunchKernelGGL(k_bottom_run, dim3(grid_of(h->batch, BE::IPB)), dim3(BE::BLOCK), 0, h->stream, h->bufs(), a);
@@ -802,7 +980,8 @@ uwvk_status uwvk_ipose_create(int64_t batch, int device, uwvk_ipose** out) {
 void uwvk_ipose_destroy(uwvk_ipose* h) {
   UWVK_DEVICE_GUARD(h);
   if (!h) return;
-  small_destroy(h);
+  small_destroy(h);  // waits for the stream first
+  stage_release(h->stages);
   delete h;
 }
 
@@ -917,21 +1096,134 @@ uwvk_status uwvk_ipose_get_corrected_pose(uwvk_ipose* h, double* out) {
   HIPCHK(hipMemcpyAsync(x.data(), h->d_mu, x.size() * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(ref.data(), h->d_aux, ref.size() * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (int64_t i = 0; i < B; i++) {
-    const double* r = &ref[i * 7];
-    const double* e = &x[i * 7];
-    double* o = out + i * 7;
-    // t = t_ref + R_ref p_err (Eigen _transformVector), q = q_ref * q_err
-    const double* q = r + 3;
-    double uv[3] = {2 * (q[2] * e[2] - q[3] * e[1]), 2 * (q[3] * e[0] - q[1] * e[2]), 2 * (q[1] * e[1] - q[2] * e[0])};
-    double t2[3] = {q[2] * uv[2] - q[3] * uv[1], q[3] * uv[0] - q[1] * uv[2], q[1] * uv[1] - q[2] * uv[0]};
-    for (int k = 0; k < 3; k++) o[k] = r[k] + (e[k] + q[0] * uv[k] + t2[k]);
-    const double* b = e + 3;
-    o[3] = q[0] * b[0] - q[1] * b[1] - q[2] * b[2] - q[3] * b[3];
-    o[4] = q[0] * b[1] + q[1] * b[0] + q[2] * b[3] - q[3] * b[2];
-    o[5] = q[0] * b[2] + q[2] * b[0] + q[3] * b[1] - q[1] * b[3];
-    o[6] = q[0] * b[3] + q[3] * b[0] + q[1] * b[2] - q[2] * b[1];
+  for (int64_t i = 0; i < B; i++) ipose_corrected(&ref[i * 7], &x[i * 7], out + i * 7);
+  return UWVK_OK;
+}
+
+// host only (no HIP call): what uwvk_ipose_run_log checks before it queues anything
+uwvk_status uwvk_ipose_log_check(const uwvk_ipose_log* log, int64_t first, int64_t count) {
+  if (!log || first < 0 || count < 0 || first > log->epochs || count > log->epochs - first) return UWVK_EINVAL;
+  if (log->n_visual < 0 || (!log->visual_offset && log->n_visual != 0)) return UWVK_EINVAL;
+  if (log->dt_epoch) {
+    for (int64_t e = first; e < first + count; e++)
+      if (!(log->dt_epoch[e] > 0.0)) return UWVK_EINVAL;
+  } else if (!(log->dt > 0.0)) {
+    return UWVK_EINVAL;
   }
+  int64_t row0 = 0, row1 = 0;
+  if (log->visual_offset) {
+    for (int64_t e = first; e <= first + count; e++) {
+      const int64_t o = log->visual_offset[e];
+      if (o < 0 || o > log->n_visual || (e > first && o < log->visual_offset[e - 1])) return UWVK_EINVAL;
+    }
+    row0 = log->visual_offset[first];
+    row1 = log->visual_offset[first + count];
+  }
+  if (row1 > row0) {
+    if (log->n_features < 1 || !log->features || !log->feature_positions) return UWVK_EINVAL;
+    if ((!log->feature_cov && !log->shared_feature_cov) || (!log->marker_pose && !log->shared_marker_pose))
+      return UWVK_EINVAL;
+  }
+  // the shared host values the range uses (checkMeasurment of the single calls)
+  if (log->dt_epoch) {
+    if (!finite_all(log->dt_epoch + first, (size_t)count)) return UWVK_ENAN;
+  } else if (!std::isfinite(log->dt)) {
+    return UWVK_ENAN;
+  }
+  if (row1 > row0) {
+    const size_t nf = (size_t)log->n_features;
+    if (!log->feature_cov && !finite_all(log->shared_feature_cov, nf * 4)) return UWVK_ENAN;
+    if (!finite_all(log->feature_positions, nf * 3)) return UWVK_ENAN;
+    if (!log->marker_pose && !finite_all(log->shared_marker_pose + row0 * 7, (size_t)(row1 - row0) * 7)) return UWVK_ENAN;
+    if (!finite_all(log->cov_marker_pose, 36) || !finite_all(log->camera, 4) || !finite_all(log->camera_in_body, 7))
+      return UWVK_ENAN;
+  }
+  return UWVK_OK;
+}
+
+uwvk_status uwvk_ipose_run_log(uwvk_ipose* h, const uwvk_ipose_log* log, int64_t first, int64_t count,
+                               uint32_t* applied, const uwvk_ipose_track* track) {
+  UWVK_DEVICE_GUARD(h);
+  if (!h) return UWVK_EINVAL;
+  const uwvk_status chk = uwvk_ipose_log_check(log, first, count);
+  if (chk != UWVK_OK) return chk;
+  if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->corrected) ||
+                track->capacity < uwvk_pose_track_records(first, count, track->every)))
+    return UWVK_EINVAL;
+  if (!h->has_state) return UWVK_ENOTINIT;
+  if (count == 0) return UWVK_OK;
+  const int64_t row0 = log->visual_offset ? log->visual_offset[first] : 0;
+  const int64_t rows = log->visual_offset ? log->visual_offset[first + count] - row0 : 0;
+  const size_t nf = rows ? (size_t)log->n_features : 0;
+  // the staged words: feature positions, shared feature covariance, this call's
+  // shared marker poses, then the epoch table
+  const size_t w_pos = nf * 3, w_cov = (rows && !log->feature_cov) ? nf * 4 : 0,
+               w_mk = (rows && !log->marker_pose) ? (size_t)rows * 7 : 0, w_all = w_pos + w_cov + w_mk;
+  StageSlot* sg = stage_acquire(h->stages, w_all * 8 + (size_t)count * sizeof(IPoseEpoch));
+  if (!sg) return UWVK_ENOMEM;
+  double* hw = (double*)sg->host;
+  const double* dw = (const double*)sg->dev;
+  if (w_pos) std::memcpy(hw, log->feature_positions, w_pos * 8);
+  if (w_cov) std::memcpy(hw + w_pos, log->shared_feature_cov, w_cov * 8);
+  if (w_mk) std::memcpy(hw + w_pos + w_cov, log->shared_marker_pose + row0 * 7, w_mk * 8);
+  IPoseEpoch* het = (IPoseEpoch*)(hw + w_all);
+  int32_t record = 0;
+  for (int64_t k = 0; k < count; k++) {
+    const int64_t e = first + k;
+    IPoseEpoch& ev = het[k];
+    ev.dt = log->dt_epoch ? log->dt_epoch[e] : log->dt;
+    ev.row = log->visual_offset ? log->visual_offset[e] : 0;
+    ev.rows = log->visual_offset ? (int32_t)(log->visual_offset[e + 1] - log->visual_offset[e]) : 0;
+    ev.record = (track && (e + 1) % track->every == 0) ? record++ : -1;
+  }
+  HIPCHK(hipMemcpyAsync(sg->dev, sg->host, w_all * 8 + (size_t)count * sizeof(IPoseEpoch), hipMemcpyHostToDevice,
+                        h->stream));
+  sg->used = true;
+  IPoseRunArgs a{};
+  a.ref_io = h->d_aux;
+  a.marker_rows = w_mk ? dw + w_pos + w_cov : nullptr;
+  a.row_base = row0;
+  a.applied = applied;
+  a.tr_mean = track ? track->mean : nullptr;
+  a.tr_var = track ? track->variance : nullptr;
+  a.tr_corr = track ? track->corrected : nullptr;
+  a.tau = h->tau;
+  a.Q = h->Q;
+  if (rows) {
+    a.va.nf = log->n_features;
+    a.va.features = log->features;
+    a.va.fcov = log->feature_cov ? log->feature_cov : dw + w_pos;
+    a.va.fcov_stride = log->feature_cov ? (int64_t)nf * 4 : 0;
+    a.va.fpos = dw;
+    a.va.marker = log->marker_pose;
+    a.va.marker_stride = log->marker_pose ? 7 : 0;
+    std::memcpy(a.va.cov_marker, log->cov_marker_pose, sizeof(a.va.cov_marker));
+    std::memcpy(a.va.cam, log->camera, sizeof(a.va.cam));
+    std::memcpy(a.va.cam_in, log->camera_in_body, sizeof(a.va.cam_in));
+  }
+  // one launch per chunk of epochs; the state's round trip through HBM is exact
+  uwvk_status st = UWVK_OK;
+  const dim3 grid(grid_of(h->batch, IAE<1>::IPB)), block(IAE<1>::BLOCK);
+  for (int64_t k = 0; k < count && st == UWVK_OK; k += kIPoseChunk) {
+    a.ev = (const IPoseEpoch*)(dw + w_all) + k;
+    a.count = (int32_t)std::min<int64_t>(kIPoseChunk, count - k);
+    a.pose_ref = log->pose_ref ? log->pose_ref + (first + k) * h->batch * 7 : nullptr;
+    if (h->so3_right) hipLaunchKernelGGL(k_ipose_run<1>, grid, block, 0, h->stream, h->bufs(), a);
+    else hipLaunchKernelGGL(k_ipose_run<0>, grid, block, 0, h->stream, h->bufs(), a);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) st = (uwvk_status)::uwvk::edevice_status(le, "k_ipose_run");
+  }
+  if (hipEventRecord(sg->done, h->stream) != hipSuccess) {  // cannot tell when the slot is free: wait now
+    (void)hipStreamSynchronize(h->stream);
+    sg->used = false;
+  }
+  return st;
+}
+
+uwvk_status uwvk_ipose_synchronize(uwvk_ipose* h) {
+  UWVK_DEVICE_GUARD(h);
+  if (!h) return UWVK_EINVAL;
+  HIPCHK(hipStreamSynchronize(h->stream));
   return UWVK_OK;
 }
 

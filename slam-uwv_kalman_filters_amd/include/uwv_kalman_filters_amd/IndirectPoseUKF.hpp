@@ -73,6 +73,16 @@ class IndirectPoseUKF {
     }
     return r;
   }
+  // Epochs [first, first + count) of a device-resident log (uwvk_ipose_run_log):
+  // per epoch updatePoseReference, predictionStep(that epoch's dt), one
+  // integrateMeasurement per visual row; bitwise that call sequence.
+  // Asynchronous on the filter's stream: the getters and synchronize wait.
+  // applied: DEVICE [batch] uint32, zeroed by the caller (nullable).
+  void runLog(const uwvk_ipose_log& log, int64_t first, int64_t count, uint32_t* applied = nullptr,
+              const uwvk_ipose_track* track = nullptr) {
+    check(uwvk_ipose_run_log(h_, &log, first, count, applied, track), "runLog");
+  }
+  void synchronize() { check(uwvk_ipose_synchronize(h_), "synchronize"); }
   void getState(std::vector<double>& x, std::vector<double>* P = nullptr) {
     x.resize((size_t)batch_ * 7);
     if (P) P->resize((size_t)batch_ * 36);

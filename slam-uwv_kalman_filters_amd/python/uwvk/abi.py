@@ -116,6 +116,17 @@ class BottomTrack(C.Structure):  # uwvk_bottom_track (device buffers)
     _fields_ = [("every", C.c_int64), ("capacity", C.c_int64), ("mean", P), ("variance", P)]
 
 
+class IPoseLog(C.Structure):  # uwvk_ipose_log (steps / offsets / shared inputs host, payloads device)
+    _fields_ = [("epochs", C.c_int64), ("dt", D), ("dt_epoch", P), ("pose_ref", P), ("visual_offset", P),
+                ("n_visual", C.c_int64), ("n_features", C.c_int32), ("features", P), ("feature_cov", P),
+                ("shared_feature_cov", P), ("feature_positions", P), ("marker_pose", P), ("shared_marker_pose", P),
+                ("cov_marker_pose", _arr(D, 36)), ("camera", _arr(D, 4)), ("camera_in_body", _arr(D, 7))]
+
+
+class IPoseTrack(C.Structure):  # uwvk_ipose_track (device buffers)
+    _fields_ = [("every", C.c_int64), ("capacity", C.c_int64), ("mean", P), ("variance", P), ("corrected", P)]
+
+
 class StreamTimes(C.Structure):  # uwvk_stream_times (host pointers)
     _fields_ = [("imu", P), ("n_imu", C.c_int64), ("dvl", P), ("n_dvl", C.c_int64),
                 ("pressure", P), ("n_pressure", C.c_int64), ("adcp", P), ("n_adcp", C.c_int64),

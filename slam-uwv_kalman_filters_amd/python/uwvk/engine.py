@@ -50,6 +50,7 @@ SYMBOLS = [
     "uwvk_pose_run_log_fixes", "uwvk_schedule_fixes",
     "uwvk_pose_run_log_delayed", "uwvk_schedule_delayed",
     "uwvk_bottom_log_check", "uwvk_bottom_run_log", "uwvk_bottom_synchronize",
+    "uwvk_ipose_log_check", "uwvk_ipose_run_log", "uwvk_ipose_synchronize",
 ]
 
 _LIB = None

@@ -7,7 +7,9 @@ UWVKError(UWVK_EDEVICE) without a gfx950 device.
 BottomUKFBatch.run_log runs a device-resident multi-epoch log
 (uwvk_bottom_run_log, DeviceBottomLog); BottomLogRecorder turns a call sequence
 into such a log's host arrays and play_bottom_log issues a host log as single
-calls to any filter object (both pure Python, no device)."""
+calls to any filter object (both pure Python, no device).
+IndirectPoseUKFBatch.run_log, DeviceIPoseLog, IPoseLogRecorder and
+play_ipose_log are the same for IndirectPoseUKF (uwvk_ipose_run_log)."""
 import ctypes as C
 
 import numpy as np
@@ -363,3 +365,229 @@ class IndirectPoseUKFBatch(_Small):
         out = np.empty((self.batch, 7))
         _chk(self._fn("get_corrected_pose")(self.h, _p(out)), "ipose_get_corrected_pose")
         return out
+
+    @property
+    def stream(self):
+        f = self._fn("stream")
+        f.restype, f.argtypes = VP, [VP]
+        return VP(f(self.h))
+
+    def upload_log(self, log):
+        return DeviceIPoseLog(log, self.device)
+
+    def synchronize(self):
+        _chk(self._fn("synchronize")(self.h), "ipose_synchronize")
+
+    def run_log(self, dlog, first=0, count=None, every=None, sync=True, applied=None, capacity=None, mean=True,
+                variance=True, corrected=True):
+        """Epochs [first, first + count) of a DeviceIPoseLog in one launch per 4096
+        epochs (uwvk_ipose_run_log): per epoch set_pose_reference, predict(dt of
+        that epoch), one update_visual per visual row.  Bitwise the single calls
+        (play_ipose_log on this class).  applied: a DeviceBuffer of [batch] uint32
+        the applied visual rows are added to.  every: a record after each
+        absolute epoch e with (e + 1) % every == 0; returns (mean
+        [records][batch][7], variance [records][batch][6], corrected
+        [records][batch][7]) (None for one switched off), read back after the run."""
+        if dlog.batch != self.batch:
+            raise ValueError("log of batch %d on a filter of batch %d" % (dlog.batch, self.batch))
+        count = dlog.epochs - first if count is None else count
+        ap = applied.ptr if applied is not None else None
+        widths = (("mean", 7, mean), ("variance", 6, variance), ("corrected", 7, corrected))
+        tr, bufs, n = None, {}, 0
+        if every is not None:
+            n = int(self.L.uwvk_pose_track_records(C.c_int64(first), C.c_int64(count), C.c_int64(every)))
+            cap = n if capacity is None else int(capacity)
+            t = abi.IPoseTrack()
+            t.every, t.capacity = int(every), cap
+            for name, w, on in widths:
+                bufs[name] = DeviceBuffer.empty(cap * self.batch * w * 8, self.device) if on else None
+                setattr(t, name, bufs[name].ptr if on else None)
+            tr = C.byref(t)
+        _chk(self._fn("run_log")(self.h, C.byref(dlog.s), C.c_int64(first), C.c_int64(count), ap, tr),
+             "ipose_run_log")
+        if sync:
+            self.synchronize()
+        if every is None:
+            return None
+        out = []
+        for name, w, _ in widths:
+            b = bufs[name]
+            out.append(None if b is None else
+                       (b.read(np.float64, (n, self.batch, w), self.stream) if n else np.empty((0, self.batch, w))))
+        return tuple(out)
+
+
+IPOSE_DEVICE_ARRAYS = ("pose_ref", "features", "feature_cov", "marker_pose")
+
+
+def ipose_log_struct(log, ptr):
+    """abi.IPoseLog of a host log (IPoseLogRecorder.log()'s layout).  ptr: the
+    addresses of its DEVICE arrays {pose_ref, features, feature_cov, marker_pose}
+    (None: absent).  Returns (struct, the host arrays it points into: keep them alive)."""
+    s = abi.IPoseLog()
+    s.epochs, s.dt = int(log["epochs"]), float(log["dt"])
+    s.n_features = int(log["n_features"])
+    keep = {}
+    for k, t in (("dt_epoch", np.float64), ("visual_offset", np.int64), ("shared_feature_cov", np.float64),
+                 ("feature_positions", np.float64), ("shared_marker_pose", np.float64)):
+        if log.get(k) is not None:
+            keep[k] = np.ascontiguousarray(log[k], dtype=t)
+        setattr(s, k, _p(keep.get(k)))
+    s.n_visual = 0 if log.get("features") is None else len(log["features"])
+    for k in IPOSE_DEVICE_ARRAYS:
+        setattr(s, k, ptr.get(k))
+    abi.fill(s.cov_marker_pose, np.asarray(log["cov_marker_pose"], float).reshape(-1))
+    abi.fill(s.camera, np.asarray(log["camera"], float).reshape(-1))
+    abi.fill(s.camera_in_body, np.asarray(log["camera_in_body"], float).reshape(-1))
+    return s, keep
+
+
+class DeviceIPoseLog:
+    """uwvk_ipose_log: the payloads (pose_ref, features, feature_cov,
+    marker_pose) in device memory, the steps, row offsets and shared inputs on
+    the host.  `log` is a dict in IPoseLogRecorder.log()'s layout."""
+
+    def __init__(self, log, device=0):
+        self.bufs, ptr = {}, {}
+        for name in IPOSE_DEVICE_ARRAYS:
+            if log.get(name) is not None and np.asarray(log[name]).size:
+                self.bufs[name] = DeviceBuffer(np.ascontiguousarray(log[name], dtype=np.float64), device)
+                ptr[name] = self.bufs[name].ptr
+        self.s, self.host = ipose_log_struct(log, ptr)
+        self.epochs = self.s.epochs
+        self.batch = int(log["batch"])
+
+
+class IPoseLogRecorder:
+    """Turns a call sequence on the oracle wrapper's IndirectPoseUKF methods into
+    the host arrays of a uwvk_ipose_log (no device).  Each predict opens an epoch
+    with the reference last set and its own dt; each update_visual appends a
+    visual row to the open epoch.  A feature covariance [nf][2][2] given to
+    every row with the same values is the log's shared one, otherwise every row
+    gets a per-instance array; a marker pose [7] on every row is the log's
+    shared one per row, otherwise per instance.
+    What the log cannot express raises ValueError: a mask, an update before the
+    first predict, a feature count that changes, feature positions, a marker
+    covariance, a camera or a camera pose that change, a reference first set
+    after the first predict, or set between an epoch's predict and one of its
+    updates (or after the last predict)."""
+
+    def __init__(self, batch):
+        self.batch = int(batch)
+        self.ref, self.ref_pending = None, False
+        self.epochs = []   # dict(ref=, dt=, rows=[(features, fcov, fcov_shared, marker, marker_shared)])
+        self.shared = None  # (feature_positions, cov_marker_pose, camera, camera_in_body)
+
+    def set_pose_reference(self, pose):
+        if self.ref is None and self.epochs:
+            raise ValueError("a reference first set after the first predict")
+        self.ref, self.ref_pending = np.array(_per(pose, self.batch, (7,))), True
+
+    def predict(self, dt):
+        self.epochs.append(dict(ref=self.ref, dt=float(dt), rows=[]))
+        self.ref_pending = False
+
+    def update_visual(self, features, feature_cov, feature_positions, marker_pose, cov_marker_pose, camera,
+                      camera_in_body, mask=None):
+        if mask is not None:
+            raise ValueError("a mask cannot be recorded")
+        if not self.epochs:
+            raise ValueError("an update before the first predict")
+        if self.ref_pending:
+            raise ValueError("a reference set between an epoch's predict and its update")
+        f = np.array(features, np.float64)
+        if f.ndim != 3 or f.shape[0] != self.batch or f.shape[2] != 2 or f.shape[1] < 1:
+            raise ValueError("features of shape %r" % (f.shape,))
+        nf = f.shape[1]
+        shared = (np.array(feature_positions, np.float64).reshape(-1, 3), np.array(cov_marker_pose, np.float64).reshape(36),
+                  np.array(camera, np.float64).reshape(4), np.array(camera_in_body, np.float64).reshape(7))
+        if len(shared[0]) != nf:
+            raise ValueError("%d feature positions for %d features" % (len(shared[0]), nf))
+        if self.shared is None:
+            self.shared = shared
+        elif len(self.shared[0]) != nf:
+            raise ValueError("the feature count changes (%d, was %d)" % (nf, len(self.shared[0])))
+        elif not all(np.array_equal(a, b) for a, b in zip(self.shared, shared)):
+            raise ValueError("feature positions, marker covariance, camera or camera pose change")
+        fc = np.array(feature_cov, np.float64)
+        fc_shared = fc.shape in ((nf, 2, 2), (nf, 4))
+        fc = fc.reshape(nf, 4) if fc_shared else fc.reshape(self.batch, nf, 4)
+        mp = np.array(marker_pose, np.float64)
+        mp_shared = mp.ndim == 1
+        self.epochs[-1]["rows"].append((f, fc, fc_shared, mp.reshape(7) if mp_shared else mp.reshape(self.batch, 7),
+                                        mp_shared))
+
+    def log(self):
+        if self.ref_pending and self.epochs:
+            raise ValueError("a reference set after the last predict")
+        E, B = len(self.epochs), self.batch
+        rows = [r for ep in self.epochs for r in ep["rows"]]
+        V = len(rows)
+        nf = len(self.shared[0]) if self.shared else 0
+        off = np.zeros(E + 1, np.int64)
+        off[1:] = np.cumsum([len(ep["rows"]) for ep in self.epochs])
+        fc_shared = V > 0 and all(r[2] and np.array_equal(r[1], rows[0][1]) for r in rows)
+        mp_shared = V > 0 and all(r[4] for r in rows)
+        dts = np.array([ep["dt"] for ep in self.epochs], np.float64)
+        one_dt = E > 0 and (dts == dts[0]).all()
+        sh = self.shared or (np.zeros((0, 3)), np.zeros(36), np.zeros(4), np.zeros(7))
+        return dict(
+            batch=B, epochs=E, dt=float(dts[0]) if one_dt else 0.0, dt_epoch=None if one_dt or E == 0 else dts,
+            pose_ref=None if self.ref is None else np.array([ep["ref"] for ep in self.epochs]).reshape(E, B, 7),
+            visual_offset=off, n_features=nf,
+            features=np.array([r[0] for r in rows]).reshape(V, B, nf, 2),
+            feature_cov=None if fc_shared or V == 0 else
+            np.array([np.broadcast_to(r[1], (B, nf, 4)) for r in rows]).reshape(V, B, nf, 4),
+            shared_feature_cov=rows[0][1].copy() if fc_shared else None,
+            feature_positions=sh[0],
+            marker_pose=None if mp_shared or V == 0 else
+            np.array([np.broadcast_to(r[3], (B, 7)) for r in rows]).reshape(V, B, 7),
+            shared_marker_pose=np.array([r[3] for r in rows]).reshape(V, 7) if mp_shared else None,
+            cov_marker_pose=sh[1].reshape(6, 6), camera=sh[2], camera_in_body=sh[3])
+
+
+def play_ipose_log(filt, log, first=0, count=None):
+    """The single calls of epochs [first, first + count) of a host log on any
+    filter with the oracle wrapper's methods, in uwvk_ipose_run_log's order, the
+    non-finite entries handled as the run handles them: an instance with a
+    non-finite feature, feature covariance or marker pose at a row is masked out
+    of that row's update (a filter that gets a mask must take the `mask`
+    keyword); an instance with a non-finite reference keeps the last finite one
+    this replay gave it (none yet: ValueError, the handle's own is not
+    readable).  Returns [batch], the visual rows issued to each instance."""
+    E, B, nf = int(log["epochs"]), int(log["batch"]), int(log["n_features"])
+    count = E - first if count is None else count
+    issued = np.zeros(B, np.int64)
+    cur = None
+    for e in range(first, first + count):
+        if log.get("pose_ref") is not None:
+            ref = np.array(log["pose_ref"][e], float)
+            bad = ~np.isfinite(ref).all(axis=1)
+            if bad.any():
+                if cur is None:
+                    raise ValueError("epoch %d: a non-finite reference before any finite one cannot be played" % e)
+                ref[bad] = cur[bad]
+            cur = ref
+            filt.set_pose_reference(ref)
+        filt.predict(float(log["dt"] if log.get("dt_epoch") is None else log["dt_epoch"][e]))
+        for row in range(int(log["visual_offset"][e]), int(log["visual_offset"][e + 1])):
+            f = np.array(log["features"][row], float)
+            good = np.isfinite(f).all(axis=(1, 2))
+            if log.get("feature_cov") is not None:
+                fc = np.array(log["feature_cov"][row], float).reshape(B, nf, 2, 2)
+                good &= np.isfinite(fc).all(axis=(1, 2, 3))
+                fc[~good] = np.eye(2)
+            else:
+                fc = np.asarray(log["shared_feature_cov"], float).reshape(nf, 2, 2)
+            if log.get("marker_pose") is not None:
+                mp = np.array(log["marker_pose"][row], float)
+                good &= np.isfinite(mp).all(axis=1)
+                mp[~good] = [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+            else:
+                mp = np.asarray(log["shared_marker_pose"][row], float)
+            f[~good] = 0.0
+            kw = {} if good.all() else dict(mask=good)
+            filt.update_visual(f, fc, log["feature_positions"], mp, log["cov_marker_pose"], log["camera"],
+                               log["camera_in_body"], **kw)
+            issued += good
+    return issued
