@@ -391,14 +391,26 @@ class PoseTwin:
         self.model_blocks = None  # shared DynamicModel's (surge,sway,yaw) blocks, None = base
 
     @classmethod
-    def from_config(cls, dof, pos, pos_cov, rot, rot_cov, cfg, uwv):
-        """PoseUKF.cpp:288-372 with imu_in_body = identity."""
+    def from_config(cls, dof, pos, pos_cov, rot, rot_cov, cfg, uwv, imu_in_body=None):
+        """PoseUKF.cpp:288-372.  imu_in_body: None (identity) or the 7-vector
+        translation + unit quaternion (w, x, y, z) of the Affine3d: the
+        translation goes into the parameter (:358), the rotation turns the bias
+        offsets (:298-299, :360-362) and the bias blocks of Sigma (:328-329)."""
         lay = Layout(dof)
         s, d = lay.s, lay.d
         x = np.zeros(lay.store)
         x[0:3], x[3:7] = pos, rot
-        x[s["bg"]:s["bg"] + 3] = cfg["gyro_bias_offset"]
-        x[s["ba"]:s["ba"] + 3] = cfg["acc_bias_offset"]
+        bg0, ba0 = np.array(cfg["gyro_bias_offset"], float), np.array(cfg["acc_bias_offset"], float)
+        Pbg = np.diag(np.square(cfg["gyro_bias_instability"]))
+        Pba = np.diag(np.square(cfg["acc_bias_instability"]))
+        lever = np.zeros(3)
+        if imu_in_body is not None:
+            ib = np.asarray(imu_in_body, float)
+            lever, Rb = ib[:3].copy(), qmat(ib[3:7])
+            bg0, ba0 = Rb @ bg0, Rb @ ba0
+            Pbg, Pba = Rb @ Pbg @ Rb.T, Rb @ Pba @ Rb.T
+        x[s["bg"]:s["bg"] + 3] = bg0
+        x[s["ba"]:s["ba"] + 3] = ba0
         x[s["grav"]] = wgs84_gravity(cfg["lat"], cfg["alt"])
         if lay.full:
             x[s["inertia"]:s["inertia"] + 9] = uwv.M[np.ix_(IDX, IDX)].ravel(order="F")
@@ -408,8 +420,8 @@ class PoseTwin:
         P = np.zeros((dof, dof))
         P[0:3, 0:3], P[3:6, 3:6] = pos_cov, rot_cov
         P[6:9, 6:9], P[9:12, 9:12] = np.eye(3), 10 * np.eye(3)
-        P[12:15, 12:15] = np.diag(np.square(cfg["gyro_bias_instability"]))
-        P[15:18, 15:18] = np.diag(np.square(cfg["acc_bias_instability"]))
+        P[12:15, 12:15] = Pbg
+        P[15:18, 15:18] = Pba
         P[18, 18] = 0.05 ** 2
         if lay.full:
             for k in ("inertia", "lin", "quad"):
@@ -418,8 +430,8 @@ class PoseTwin:
             P[d[k]:d[k] + 2, d[k]:d[k] + 2] = cfg["wv_limits"] ** 2 * np.eye(2)
         P[d["badcp"]:d["badcp"] + 2, d["badcp"]:d["badcp"] + 2] = cfg["adcp_limits"] ** 2 * np.eye(2)
         P[d["rho"], d["rho"]] = cfg["rho_limits"] ** 2
-        param = dict(imu_in_body=np.zeros(3), gyro_bias_offset=np.array(cfg["gyro_bias_offset"]),
-                     gyro_bias_tau=cfg["gyro_tau"], acc_bias_offset=np.array(cfg["acc_bias_offset"]),
+        param = dict(imu_in_body=lever, gyro_bias_offset=bg0,
+                     gyro_bias_tau=cfg["gyro_tau"], acc_bias_offset=ba0,
                      acc_bias_tau=cfg["acc_tau"], inertia_tau=cfg["inertia_tau"], lin_damping_tau=cfg["lin_tau"],
                      quad_damping_tau=cfg["quad_tau"], water_velocity_tau=cfg["wv_tau"],
                      water_velocity_scale=cfg["wv_scale"], adcp_bias_tau=cfg["adcp_tau"],
@@ -427,8 +439,10 @@ class PoseTwin:
         f = cls(dof, x, P, (cfg["lat"], cfg["lon"]), uwv, param)
         return f
 
-    def set_noise_from_config(self, cfg, dt):
-        """PoseUKF.cpp:393-439 (imu_in_body = identity)."""
+    def set_noise_from_config(self, cfg, dt, q_imu_in_body=None):
+        """PoseUKF.cpp:393-439.  q_imu_in_body: None (identity) or the unit
+        quaternion (w, x, y, z) whose matrix turns the orientation, gyro-bias
+        and acc-bias blocks (:396, :409-413)."""
         lay, d = self.lay, self.lay.d
         Q = np.zeros((lay.dof, lay.dof))
         j = np.asarray(cfg["max_jerk"], float)
@@ -447,6 +461,13 @@ class PoseTwin:
         Q[d["badcp"]:d["badcp"] + 2, d["badcp"]:d["badcp"] + 2] = (2.0 / (cfg["adcp_tau"] * dt) *
                                                                    cfg["adcp_limits"] ** 2 * np.eye(2))
         Q[d["rho"], d["rho"]] = 2.0 / (cfg["rho_tau"] * dt) * cfg["rho_limits"] ** 2
+        if q_imu_in_body is not None:
+            Rb = qmat(np.asarray(q_imu_in_body, float))
+            Q[3:6, 3:6] = Rb @ np.diag(np.square(cfg["gyro_randomwalk"])) @ Rb.T
+            Q[12:15, 12:15] = Rb @ ((2.0 / (cfg["gyro_tau"] * dt)) *
+                                    np.diag(np.square(cfg["gyro_bias_instability"]))) @ Rb.T
+            Q[15:18, 15:18] = Rb @ ((2.0 / (cfg["acc_tau"] * dt)) *
+                                    np.diag(np.square(cfg["acc_bias_instability"]))) @ Rb.T
         self.Q = Q
 
     # -- process model, PoseUKF.cpp:12-84 (vectorised over sigma points)
