@@ -57,7 +57,9 @@ extern "C" {
  *      uwvk_schedule_delayed; uwvk_bottom_log, uwvk_bottom_track, UWVK_BEV_*,
  *      uwvk_bottom_log_check, uwvk_bottom_run_log, uwvk_bottom_synchronize;
  *      uwvk_vel_get_status; uwvk_ipose_log, uwvk_ipose_track,
- *      uwvk_ipose_log_check, uwvk_ipose_run_log, uwvk_ipose_synchronize. */
+ *      uwvk_ipose_log_check, uwvk_ipose_run_log, uwvk_ipose_synchronize;
+ *      uwvk_vel_log_host, uwvk_vel_track, uwvk_vel_log_check,
+ *      uwvk_vel_run_log_track. */
 #define UWVK_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
@@ -811,17 +813,21 @@ uwvk_status uwvk_vel_get_state(uwvk_vel* h, double* x, double* P);
 uwvk_status uwvk_vel_get_model_state(uwvk_vel* h, double* out);
 /* Per-instance status words: waits for the handle's stream, copies batch words
  * and, if clear, zeroes the device words (as the pose and bottom getters do).
- * NULL handle or status: UWVK_EINVAL.  The only bit VelocityUKF raises today:
+ * NULL handle or status: UWVK_EINVAL.  The bits VelocityUKF raises:
+ *  - UWVK_ST_NAN, sticky until cleared, by uwvk_vel_run_log_track alone: a
+ *    non-finite sample or input of that instance was skipped.
  *  - UWVK_ST_NOTPD, sticky until cleared: the Cholesky factorisation at the
  *    start of a predict or an update (single calls and every run_log epoch
  *    alike) met a non-positive pivot.  The step is NOT skipped: the flagged
  *    instance's state and covariance are overwritten and unspecified from then
  *    on (unlike BottomUKF, which keeps the state it had); re-initialise it.
  *    The other instances are unaffected.
- *  - A non-finite sample in a device-resident log is not screened (the single
- *    calls reject one with UWVK_ENAN; run_log cannot): it enters that
- *    instance's state and surfaces as UWVK_ST_NOTPD at the next step's
- *    factorisation, so a bad sample in a run's LAST step leaves no bit. */
+ *  - uwvk_vel_run_log does not screen the samples of its device-resident log
+ *    (the single calls reject a non-finite one with UWVK_ENAN): a bad sample
+ *    enters that instance's state and surfaces as UWVK_ST_NOTPD at the next
+ *    step's factorisation, so one in a run's LAST step leaves no bit.  Use
+ *    uwvk_vel_run_log_track (below) for logs that may hold drop-outs: it skips
+ *    the bad sample for that instance and raises UWVK_ST_NAN. */
 uwvk_status uwvk_vel_get_status(uwvk_vel* h, uint32_t* status, int clear);
 
 typedef struct uwvk_vel_log {
@@ -841,6 +847,74 @@ typedef struct uwvk_vel_log {
  * registers across the launch.  Asynchronous on the handle's stream (the
  * getters and uwvk_vel_synchronize wait). */
 uwvk_status uwvk_vel_run_log(uwvk_vel* h, const uwvk_vel_log* log, int64_t first, int64_t count);
+
+/* ---- VelocityUKF in a run, screened and with records --------------------- */
+/* HOST mirror of the log's device index arrays (required): what lets the call
+ * check flags and row indices before it queues anything.  It must equal the
+ * device arrays; the kernels read the device ones. */
+typedef struct uwvk_vel_log_host {
+  const uint32_t* flags;                /* HOST [log->epochs], must equal log->flags */
+  const int32_t*  dvl_index;            /* HOST [epochs] (NULL if UWVK_EV_DVL never set) */
+  int64_t         n_dvl;                /* rows of log->dvl */
+  const int32_t*  pressure_index;       /* HOST [epochs] (NULL if UWVK_EV_PRESSURE never set) */
+  int64_t         n_pressure;           /* rows of log->pressure */
+} uwvk_vel_log_host;
+
+typedef struct uwvk_vel_track {
+  int64_t every, capacity;              /* as uwvk_pose_track / uwvk_bottom_track: a record after each absolute
+                                           epoch e with (e + 1) % every == 0; capacity in records */
+  double* mean;                         /* DEVICE [records][batch][4]   nullable */
+  double* variance;                     /* DEVICE [records][batch][4]   diag(Sigma), nullable */
+  double* model;                        /* DEVICE [records][batch][13]  layout of uwvk_vel_get_model_state, nullable */
+} uwvk_vel_track;
+
+/* host only, no device needed: the checks uwvk_vel_run_log_track makes before
+ * it queues anything, over epochs [first, first + count).
+ * UWVK_EINVAL: log or host NULL; a negative range or one past log->epochs; dt
+ * not finite or not > 0; host->flags, log->flags, gyro or efforts NULL while
+ * count > 0; a host flag bit other than UWVK_EV_DVL | UWVK_EV_PRESSURE; a
+ * flagged kind whose host index, device index or payload pointer is NULL; a
+ * host index outside [0, n_kind) at a flagged epoch of the range.
+ * UWVK_ENAN: a non-finite dvl_cov or pressure_cov that a flagged epoch of the
+ * range uses. */
+uwvk_status uwvk_vel_log_check(const uwvk_vel_log* log, const uwvk_vel_log_host* host,
+                               int64_t first, int64_t count);
+
+/* Epochs [first, first + count) of the log, each as uwvk_vel_run_log runs it
+ * (gyro, efforts, predict, DVL, pressure), on the layout UWVK_VEL_OPT_LANE_GROUPS
+ * selects for that call, one launch per 4096 epochs, asynchronous on the
+ * handle's stream.  A record of every instance (any of mean, diag(Sigma), the
+ * motion-model state) is written after all updates of each record epoch, by the
+ * epoch kernel from the state it holds: a record does not end a launch.  Record
+ * r of the call is the r-th record epoch inside the range, so the records of
+ * calls over adjacent ranges concatenate to those of one call.
+ *
+ * For an instance whose samples are all finite, (x, P), the motion-model state,
+ * the status word and the handle's stored gyro / efforts are bitwise those of
+ * uwvk_vel_run_log on the same layout over the same range, and every record is
+ * bitwise uwvk_vel_get_state / uwvk_vel_get_model_state with that run cut
+ * after the record's epoch.  count == 0 changes nothing.
+ *
+ * Screening, per instance (the others stay bitwise as beside a clean log):
+ *  - a non-finite DVL or pressure sample: that update is skipped for that
+ *    instance (the single call with the instance masked out), UWVK_ST_NAN;
+ *  - a non-finite gyro or efforts component at an epoch: the instance skips
+ *    that epoch's predict (filter, side motion model and its rate keep what
+ *    they had), UWVK_ST_NAN; the epoch's updates still run.  The gyro / efforts
+ *    the call leaves in the handle are those of the instance's last epoch with
+ *    finite inputs (none: unchanged);
+ *  - UWVK_ST_NOTPD as in uwvk_vel_run_log: the step is not skipped.
+ * applied (DEVICE [batch][2], nullable, zeroed by the caller): the DVL and
+ * pressure updates not skipped for the instance are added to it.
+ *
+ * Returns uwvk_vel_log_check's result first, then UWVK_EINVAL for a track with
+ * every <= 0, all three buffers NULL or capacity < uwvk_pose_track_records(
+ * first, count, every), then UWVK_ENOMODEL before uwvk_vel_setup_motion_model,
+ * all with nothing queued and the state untouched. */
+uwvk_status uwvk_vel_run_log_track(uwvk_vel* h, const uwvk_vel_log* log, const uwvk_vel_log_host* host,
+                                   int64_t first, int64_t count,
+                                   uint32_t* applied /* DEVICE [batch][2] DVL, pressure; nullable, caller zeroes */,
+                                   const uwvk_vel_track* track /* nullable */);
 /* UWVK_VEL_OPT_LANE_GROUPS: -1 (default) auto by batch size, 0 one filter per
  * lane (9 sigma points in one lane's registers), 1 one filter per 16-lane DPP
  * row (one sigma point per lane; fills the chip at small batches, e.g. C2's 4096);

@@ -498,6 +498,127 @@ __global__ __launch_bounds__(64) void k_vel_epoch(VelBufs b, VelShared P0, VelEp
   v_store(b, i, mu, S);
 }
 
+// ---- uwvk_vel_run_log_track: the same epochs, screened, with records ---------
+// What the screened kernels take beside VelEpochArgs.  The record epochs of a
+// launch are next, next + every, ...: the host places the first one, so the
+// kernels compare and add (no 64-bit modulo per epoch).
+struct VelTrackArgs {
+  uint32_t* applied;  // [batch][2] DVL, pressure updates applied (nullable)
+  double* mean;       // [records][batch][4]   (nullable)
+  double* variance;   // [records][batch][4]   diag(Sigma) (nullable)
+  double* model;      // [records][batch][13]  (nullable)
+  int64_t next;       // first record epoch >= ea.first (absolute), -1 = no track
+  int64_t every;
+  int64_t record;     // index of that record in the call's buffers
+};
+
+template <int N>
+UWVK_DEV bool v_finite(const double (&a)[N]) {
+  bool f = true;
+#pragma unroll
+  for (int k = 0; k < N; k++) f = f && isfinite(a[k]);
+  return f;
+}
+
+UWVK_DEV void v_record(const VelTrackArgs& ta, int64_t at, const double mu[4], const double S[16],
+                       const double m[13]) {
+  if (ta.mean) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) ta.mean[at * 4 + k] = mu[k];
+  }
+  if (ta.variance) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) ta.variance[at * 4 + k] = S[k * 5];
+  }
+  if (ta.model) {
+#pragma unroll
+    for (int k = 0; k < 13; k++) ta.model[at * 13 + k] = m[k];
+  }
+}
+
+// k_vel_epoch with per-lane screening (lane-divergent branches around the same
+// device functions on the same values) and records from the lane's registers.
+// w / tau start as the handle's stored inputs, so that an instance without a
+// finite epoch writes back what was there.
+__global__ __launch_bounds__(64) void k_vel_epoch_track(VelBufs b, VelShared P0, VelEpochArgs ea, VelTrackArgs ta) {
+  VEL_PARAMS(b, P0);
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= b.batch) return;
+  const int64_t B = b.batch;
+  double mu[4], S[16], m[13], w[3], tau[6];
+  v_load(b, i, mu, S);
+#pragma unroll
+  for (int k = 0; k < 13; k++) m[k] = b.model[i * 13 + k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) w[k] = b.gyro[i * 3 + k];
+#pragma unroll
+  for (int k = 0; k < 6; k++) tau[k] = b.efforts[i * 6 + k];
+  bool ok = true;
+  uint32_t st = 0, n_dvl = 0, n_p = 0;
+  int64_t rec_e = ta.next, rec = ta.record;
+  for (int64_t e = ea.first; e < ea.first + ea.count; e++) {
+    double wn[3], tn[6];
+#pragma unroll
+    for (int k = 0; k < 3; k++) wn[k] = ea.gyro[(e * B + i) * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) tn[k] = ea.efforts[(e * B + i) * 6 + k];
+    if (v_finite(wn) && v_finite(tn)) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) { w[k] = wn[k]; m[10 + k] = w[k]; }
+#pragma unroll
+      for (int k = 0; k < 6; k++) tau[k] = tn[k];
+      ok = v_predict(P, mu, S, m, w, tau, ea.dt) && ok;
+      double n[13];
+      v_rk4(P, tau, ea.dt, m, n);
+#pragma unroll
+      for (int k = 0; k < 13; k++) m[k] = n[k];
+    } else {
+      st |= UWVK_ST_NAN;  // the epoch's predict is skipped: filter, side model and stored inputs stay
+    }
+    const uint32_t fl = ea.flags[e];
+    if (fl & UWVK_EV_DVL) {
+      const double* z = ea.dvl + ((int64_t)ea.dvl_index[e] * B + i) * 3;
+      const double zz[3] = {z[0], z[1], z[2]};
+      if (v_finite(zz)) {
+        ok = v_update<3, 0>(mu, S, zz, ea.dvl_cov) && ok;
+        n_dvl++;
+      } else {
+        st |= UWVK_ST_NAN;
+      }
+    }
+    if (fl & UWVK_EV_PRESSURE) {
+      const double zz[1] = {ea.pressure[(int64_t)ea.p_index[e] * B + i]};
+      const double R[1] = {ea.p_cov};
+      if (v_finite(zz)) {
+        ok = v_update<1, 3>(mu, S, zz, R) && ok;
+        n_p++;
+      } else {
+        st |= UWVK_ST_NAN;
+      }
+    }
+    if (e == rec_e) {
+      v_record(ta, rec * B + i, mu, S, m);
+      rec++;
+      rec_e += ta.every;
+    }
+  }
+  if (ea.count > 0) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) b.gyro[i * 3 + k] = w[k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) b.efforts[i * 6 + k] = tau[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 13; k++) b.model[i * 13 + k] = m[k];
+  if (!ok) st |= UWVK_ST_NOTPD;
+  if (st) b.status[i] |= st;
+  if (ta.applied) {
+    ta.applied[i * 2] += n_dvl;
+    ta.applied[i * 2 + 1] += n_p;
+  }
+  v_store(b, i, mu, S);
+}
+
 // ---------------------------------------------------------------------------
 // Lane-group epoch kernel: 16 lanes (one DPP row) per filter, ONE SIGMA POINT
 // PER LANE (lanes 0..8), lane 9 advances the side motion model
@@ -792,6 +913,143 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG 
     if (!ok) b.status[i] |= UWVK_ST_NOTPD;
     v_store(b, i, mu, S);
   }
+}
+
+// k_vel_epoch_g with screening and records (uwvk_vel_run_log_track).  One
+// filter per DPP row, so a skip is uniform within a row and not within the
+// wave: the skipped steps sit in row-uniform branches, and every cross-lane
+// operation inside them (row_sum16, row_bcast_c, the DPP moves) reads lanes of
+// its own row, which took the same branch.  The samples are the same address
+// in every lane of a row, so the finite tests are row-uniform by construction.
+// The fetch one epoch ahead stays; the fetched inputs are tested when they
+// become current.  The side lane (9) holds m and a replica of mu / Sigma and
+// writes the records; dead rows and the VG = 32 shadow row store nothing.
+template <int VG>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG / 16))) void k_vel_epoch_g_track(VelBufs b, VelShared P0, VelEpochArgs ea, VelTrackArgs ta) {
+  VEL_PARAMS(b, P0);
+  const int g = (int)threadIdx.x & 15;
+  const int64_t B = b.batch, inst = (int64_t)blockIdx.x * (64 / VG) + (int)threadIdx.x / VG;
+  const bool live = inst < B;
+  const int64_t i = live ? inst : B - 1;  // dead groups compute on a copy and store nothing
+  const bool pt = g < 9, side = g == 9;
+  const bool writer = side && live && !(VG == 32 && (threadIdx.x & 16));
+  double mu[4], S[16], m[13], w[3], tau[6];
+  v_load(b, i, mu, S);
+#pragma unroll
+  for (int k = 0; k < 13; k++) m[k] = b.model[i * 13 + k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) w[k] = b.gyro[i * 3 + k];  // what an instance without a finite epoch writes back
+#pragma unroll
+  for (int k = 0; k < 6; k++) tau[k] = b.efforts[i * 6 + k];
+  double q[4] = {m[3], m[4], m[5], m[6]};
+  bool ok = true;
+  uint32_t st = 0, n_dvl = 0, n_p = 0;
+  int64_t rec_e = ta.next, rec = ta.record;
+  double w_n[3] = {0, 0, 0}, tau_n[6] = {0, 0, 0, 0, 0, 0};
+  uint32_t fl_n = 0;
+  auto fetch = [&](int64_t e) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) w_n[k] = ea.gyro[(e * B + i) * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) tau_n[k] = ea.efforts[(e * B + i) * 6 + k];
+    fl_n = ea.flags[e + (g >> 4)];  // a lane-dependent (zero) offset: a VGPR until used
+  };
+  if (ea.count > 0) fetch(ea.first);
+  for (int64_t e = ea.first; e < ea.first + ea.count; e++) {
+    const uint32_t fl = __builtin_amdgcn_readfirstlane(fl_n);
+    const bool fin = v_finite(w_n) && v_finite(tau_n);
+    if (fin) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) { w[k] = w_n[k]; m[10 + k] = w[k]; }
+#pragma unroll
+      for (int k = 0; k < 6; k++) tau[k] = tau_n[k];
+    }
+    if (e + 1 < ea.first + ea.count) fetch(e + 1);
+    if (fin) {
+      // predict (VelocityUKF.cpp:115-128): point lanes integrate their sigma
+      // point, lane 9 the side model, in one RK4 pass
+      double L[16], x[4];
+      ok = v_chol(S, L) && ok;
+      vg_point(mu, L, g, x);
+      double s13[13], n13[13];
+#pragma unroll
+      for (int k = 0; k < 13; k++) s13[k] = m[k];
+      if (!side) {
+        s13[0] = s13[1] = s13[2] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) s13[3 + k] = q[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) s13[7 + k] = x[k];
+      }
+      v_rk4(P, tau, ea.dt, s13, n13);
+      {  // processMotionModel tail (VelocityUKF.cpp:22-32)
+        double t[3], r[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) t[k] = x[k] + (n13[7 + k] - x[k]);
+        qrot(q, t, r);
+        x[3] = x[3] + ea.dt * r[2];
+        x[0] = t[0]; x[1] = t[1]; x[2] = t[2];
+      }
+      vg_mean<4>(x, pt, mu);
+      vg_cov(x, mu, pt, S);
+      {  // Q0 by scalar loads here, not hoisted out of the loop into 32 SGPRs held across it
+        const auto& PQ = vlaunder(P);
+#pragma unroll
+        for (int k = 0; k < 16; k++) S[k] += ea.dt * PQ.Q0[k];
+      }
+      if (side) {
+#pragma unroll
+        for (int k = 0; k < 13; k++) m[k] = n13[k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) q[k] = row_bcast_c<9>(side ? m[3 + k] : 0.0);
+    } else {
+      st |= UWVK_ST_NAN;  // the epoch's predict is skipped: filter, side model and stored inputs stay
+    }
+    if (fl & UWVK_EV_DVL) {
+      const double* z = ea.dvl + ((int64_t)ea.dvl_index[e] * B + i) * 3;
+      const double zz[3] = {z[0], z[1], z[2]};
+      if (v_finite(zz)) {
+        const double* Rd = ea.dvl_cov;
+        asm volatile("" : "+s"(Rd));  // R loaded in the branch, not held in SGPRs across the loop
+        ok = vg_update<3, 0>(mu, S, zz, Rd, g) && ok;
+        n_dvl++;
+      } else {
+        st |= UWVK_ST_NAN;
+      }
+    }
+    if (fl & UWVK_EV_PRESSURE) {
+      const double zz[1] = {ea.pressure[(int64_t)ea.p_index[e] * B + i]};
+      const double R[1] = {ea.p_cov};
+      if (v_finite(zz)) {
+        ok = vg_update<1, 3>(mu, S, zz, R, g) && ok;
+        n_p++;
+      } else {
+        st |= UWVK_ST_NAN;
+      }
+    }
+    if (e == rec_e) {
+      if (writer) v_record(ta, rec * B + i, mu, S, m);
+      rec++;
+      rec_e += ta.every;
+    }
+  }
+  if (!writer) return;
+  if (ea.count > 0) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) b.gyro[i * 3 + k] = w[k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) b.efforts[i * 6 + k] = tau[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 13; k++) b.model[i * 13 + k] = m[k];
+  if (!ok) st |= UWVK_ST_NOTPD;
+  if (st) b.status[i] |= st;
+  if (ta.applied) {
+    ta.applied[i * 2] += n_dvl;
+    ta.applied[i * 2 + 1] += n_p;
+  }
+  v_store(b, i, mu, S);
 }
 
 __global__ void k_vel_setup(VelBufs b) {  // setupMotionModel pose (VelocityUKF.cpp:65-74)
@@ -1103,6 +1361,79 @@ uwvk_status uwvk_vel_run_log(uwvk_vel* h, const uwvk_vel_log* log, int64_t first
                          h->P, ea);
     else
       hipLaunchKernelGGL(k_vel_epoch, dim3(vgrid(h->batch)), dim3(64), 0, h->stream, vbufs(h), h->P, ea);
+    HIPCHK(hipGetLastError());
+  }
+  return UWVK_OK;
+}
+
+// host only (no HIP call): what uwvk_vel_run_log_track checks before it queues anything
+uwvk_status uwvk_vel_log_check(const uwvk_vel_log* log, const uwvk_vel_log_host* host, int64_t first, int64_t count) {
+  if (!log || !host) return UWVK_EINVAL;
+  if (first < 0 || count < 0 || first > log->epochs || count > log->epochs - first) return UWVK_EINVAL;
+  if (!std::isfinite(log->dt) || !(log->dt > 0.0)) return UWVK_EINVAL;
+  if (count > 0 && (!host->flags || !log->flags || !log->gyro || !log->efforts)) return UWVK_EINVAL;
+  uint32_t used = 0;
+  for (int64_t e = first; e < first + count; e++) {
+    const uint32_t f = host->flags[e];
+    if (f & ~(uint32_t)(UWVK_EV_DVL | UWVK_EV_PRESSURE)) return UWVK_EINVAL;
+    if (f & UWVK_EV_DVL) {
+      if (!host->dvl_index || !log->dvl_index || !log->dvl) return UWVK_EINVAL;
+      if (host->dvl_index[e] < 0 || host->dvl_index[e] >= host->n_dvl) return UWVK_EINVAL;
+    }
+    if (f & UWVK_EV_PRESSURE) {
+      if (!host->pressure_index || !log->pressure_index || !log->pressure) return UWVK_EINVAL;
+      if (host->pressure_index[e] < 0 || host->pressure_index[e] >= host->n_pressure) return UWVK_EINVAL;
+    }
+    used |= f;
+  }
+  // the shared covariances the flagged epochs use (checkMeasurment of the single calls)
+  if ((used & UWVK_EV_DVL) && !finite_all(log->dvl_cov, 9)) return UWVK_ENAN;
+  if ((used & UWVK_EV_PRESSURE) && !std::isfinite(log->pressure_cov)) return UWVK_ENAN;
+  return UWVK_OK;
+}
+
+uwvk_status uwvk_vel_run_log_track(uwvk_vel* h, const uwvk_vel_log* log, const uwvk_vel_log_host* host, int64_t first,
+                                   int64_t count, uint32_t* applied, const uwvk_vel_track* track) {
+  UWVK_DEVICE_GUARD(h);
+  if (!h) return UWVK_EINVAL;
+  const uwvk_status chk = uwvk_vel_log_check(log, host, first, count);
+  if (chk != UWVK_OK) return chk;
+  if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->model) ||
+                track->capacity < uwvk_pose_track_records(first, count, track->every)))
+    return UWVK_EINVAL;
+  if (!h->has_model) return UWVK_ENOMODEL;
+  VelEpochArgs ea{};
+  ea.flags = log->flags; ea.gyro = log->gyro; ea.efforts = log->efforts;
+  ea.dvl_index = log->dvl_index; ea.dvl = log->dvl;
+  std::memcpy(ea.dvl_cov, log->dvl_cov, sizeof(ea.dvl_cov));
+  ea.p_index = log->pressure_index; ea.pressure = log->pressure; ea.p_cov = log->pressure_cov;
+  ea.dt = log->dt;
+  VelTrackArgs ta{};
+  ta.applied = applied;
+  ta.next = -1;
+  if (track) {
+    ta.mean = track->mean; ta.variance = track->variance; ta.model = track->model;
+    ta.every = track->every;
+  }
+  // one launch per chunk of epochs, the layout choice of uwvk_vel_run_log; a
+  // record does not end a launch
+  const bool groups = h->groups > 0 || (h->groups < 0 && h->batch <= kVelGroupsMaxBatch);
+  constexpr int64_t kChunk = 4096;
+  for (int64_t e = first; e < first + count; e += kChunk) {
+    ea.first = e;
+    ea.count = std::min<int64_t>(kChunk, first + count - e);
+    if (track) {
+      ta.next = e + (track->every - 1 - e % track->every);
+      ta.record = uwvk_pose_track_records(first, e - first, track->every);
+    }
+    if (groups && h->groups == 2)
+      hipLaunchKernelGGL(k_vel_epoch_g_track<32>, dim3((unsigned)((h->batch + 1) / 2)), dim3(64), 0, h->stream,
+                         vbufs(h), h->P, ea, ta);
+    else if (groups)
+      hipLaunchKernelGGL(k_vel_epoch_g_track<16>, dim3((unsigned)((h->batch + 3) / 4)), dim3(64), 0, h->stream,
+                         vbufs(h), h->P, ea, ta);
+    else
+      hipLaunchKernelGGL(k_vel_epoch_track, dim3(vgrid(h->batch)), dim3(64), 0, h->stream, vbufs(h), h->P, ea, ta);
     HIPCHK(hipGetLastError());
   }
   return UWVK_OK;

@@ -767,6 +767,22 @@ class VelocityUKF {
                                    m.mask.empty() ? nullptr : m.mask.data()),
           "integrateMeasurement(Pressure)");
   }
+  // UWVK_VEL_OPT_LANE_GROUPS: the layout of runLog / runLogTrack (-1 auto by
+  // batch, 0 one filter per lane: the single calls' arithmetic, 1 one per 16 lanes)
+  void setLaneGroups(int value) { check(uwvk_vel_set_option(h_, UWVK_VEL_OPT_LANE_GROUPS, value), "setLaneGroups"); }
+  // ---- a device-resident log (uwvk_vel_log: every array in device memory) ----
+  // epochs [first, first + count), asynchronous on the handle's stream; the getters wait
+  void runLog(const uwvk_vel_log& log, int64_t first, int64_t count) {
+    check(uwvk_vel_run_log(h_, &log, first, count), "runLog");
+  }
+  // the same, checked on the host against the mirror of the log's index arrays,
+  // non-finite samples skipped per instance (UWVK_ST_NAN), with track records
+  // written by the epoch kernel (uwvk_vel_run_log_track); applied: DEVICE [batch][2]
+  void runLogTrack(const uwvk_vel_log& log, const uwvk_vel_log_host& host, int64_t first, int64_t count,
+                   uint32_t* applied = nullptr, const uwvk_vel_track* track = nullptr) {
+    check(uwvk_vel_run_log_track(h_, &log, &host, first, count, applied, track), "runLogTrack");
+  }
+  void synchronize() { check(uwvk_vel_synchronize(h_), "synchronize"); }
   void getState(std::vector<double>& x, std::vector<double>* P = nullptr) {
     x.resize((size_t)batch_ * 4);
     if (P) P->resize((size_t)batch_ * 16);

@@ -97,6 +97,15 @@ class VelLog(C.Structure):  # uwvk_vel_log (device pointers)
                 ("pressure_index", P), ("pressure", P), ("pressure_cov", D)]
 
 
+class VelLogHost(C.Structure):  # uwvk_vel_log_host (host mirror of the log's index arrays)
+    _fields_ = [("flags", P), ("dvl_index", P), ("n_dvl", C.c_int64), ("pressure_index", P),
+                ("n_pressure", C.c_int64)]
+
+
+class VelTrack(C.Structure):  # uwvk_vel_track (device buffers)
+    _fields_ = [("every", C.c_int64), ("capacity", C.c_int64), ("mean", P), ("variance", P), ("model", P)]
+
+
 BOTTOM_MAX_BEAMS = 8   # UWVK_BOTTOM_MAX_BEAMS
 BEV_NORMAL = 0x100     # UWVK_BEV_NORMAL
 

@@ -51,6 +51,7 @@ SYMBOLS = [
     "uwvk_pose_run_log_delayed", "uwvk_schedule_delayed",
     "uwvk_bottom_log_check", "uwvk_bottom_run_log", "uwvk_bottom_synchronize",
     "uwvk_ipose_log_check", "uwvk_ipose_run_log", "uwvk_ipose_synchronize",
+    "uwvk_vel_log_check", "uwvk_vel_run_log_track",
 ]
 
 _LIB = None
@@ -687,6 +688,48 @@ class VelocityUKFBatch:
         if sync:
             self.synchronize()
 
+    @property
+    def stream(self):
+        return self.L.uwvk_vel_stream(self.h)
+
+    def log_check(self, log, first=0, count=None):
+        """vel_log_check (host only, below) -> the status code."""
+        return vel_log_check(log, first, count)
+
+    def run_log_track(self, dlog, every=None, first=0, count=None, mean=True, variance=True, model=False,
+                      applied=False, sync=True, capacity=None):
+        """run_log with the log checked on the host first, non-finite samples
+        screened per instance (UWVK_ST_NAN) and, with `every`, a record of all
+        instances after every absolute epoch e with (e + 1) % every == 0, written
+        by the epoch kernel itself (uwvk_vel_run_log_track).  For finite samples
+        bitwise run_log.  applied=True counts the DVL / pressure updates not
+        skipped.  The records stay in device memory; the returned VelTrack
+        reads them back.  capacity: records to allocate for (default: what the
+        range takes)."""
+        count = dlog.epochs - first if count is None else count
+        bufs = dict(mean=None, variance=None, model=None, applied=None)
+        tr, n = None, 0
+        if every is not None:
+            n = int(self.L.uwvk_pose_track_records(C.c_int64(first), C.c_int64(count), C.c_int64(every)))
+            cap = n if capacity is None else int(capacity)
+            t = abi.VelTrack()
+            t.every, t.capacity = int(every), cap
+            for name, on, w in (("mean", mean, 4), ("variance", variance, 4), ("model", model, 13)):
+                if on:
+                    bufs[name] = DeviceBuffer.empty(max(cap, 0) * self.batch * w * 8, self.device)
+                setattr(t, name, bufs[name].ptr if on else None)
+            tr = C.byref(t)
+        if applied:
+            bufs["applied"] = DeviceBuffer(np.zeros((self.batch, 2), np.uint32), self.device)
+        _chk(self.L.uwvk_vel_run_log_track(self.h, C.byref(dlog.s), C.byref(dlog.hs), C.c_int64(first),
+                                           C.c_int64(count), bufs["applied"].ptr if applied else None, tr),
+             "vel_run_log_track")
+        if sync:
+            self.synchronize()
+        epochs = np.zeros(0, np.int64) if every is None else \
+            (np.arange(first // every + 1, first // every + 1 + n, dtype=np.int64) * every - 1)
+        return VelTrack(self, epochs, bufs)
+
     def set_process_noise(self, Q):
         """setProcessNoiseCovariance [EXT base]: 4x4 shared by the batch."""
         Q = _f64(Q)
@@ -708,28 +751,92 @@ class VelocityUKFBatch:
         return ms.value
 
 
+def vel_log_struct(log, ptr):
+    """(abi.VelLog, abi.VelLogHost, the host arrays they point into: keep them
+    alive) of a host log in synth.make_vel_log's layout.  ptr: the addresses of
+    the log's DEVICE arrays {flags, gyro, efforts, dvl_index, dvl,
+    pressure_index, pressure} (None: absent)."""
+    s, hs = abi.VelLog(), abi.VelLogHost()
+    s.epochs, s.dt = int(log["epochs"]), float(log["dt"])
+    for k in ("flags", "gyro", "efforts", "dvl_index", "dvl", "pressure_index", "pressure"):
+        setattr(s, k, ptr.get(k))
+    abi.fill(s.dvl_cov, np.asarray(log["dvl_cov"], float).ravel())
+    s.pressure_cov = float(log["pressure_cov"])
+    keep = {k: np.array(log[k], dtype=t, order="C") for k, t in  # copies: the mirror is this object's own
+            (("flags", np.uint32), ("dvl_index", np.int32), ("pressure_index", np.int32)) if log.get(k) is not None}
+    hs.flags, hs.dvl_index, hs.pressure_index = (_p(keep.get(k)) for k in ("flags", "dvl_index", "pressure_index"))
+    hs.n_dvl, hs.n_pressure = len(log["dvl"]), len(log["pressure"])
+    return s, hs, keep
+
+
 class DeviceVelLog:
+    """uwvk_vel_log with every array resident in device memory, and the host
+    mirror of its flags and row indices (uwvk_vel_log_host: `hs`, the arrays in
+    `host`, the row counts in hs.n_dvl / hs.n_pressure) that
+    VelocityUKFBatch.run_log_track and log_check need."""
+
     def __init__(self, log, device=0):
-        self.bufs = {}
-        s = abi.VelLog()
-        s.epochs, s.dt = int(log["epochs"]), float(log["dt"])
+        self.bufs, ptr = {}, {}
+        for name, dtype in (("flags", np.uint32), ("gyro", np.float64), ("efforts", np.float64),
+                            ("dvl_index", np.int32), ("dvl", np.float64), ("pressure_index", np.int32),
+                            ("pressure", np.float64)):
+            self.bufs[name] = DeviceBuffer(np.ascontiguousarray(log[name], dtype=dtype), device)
+            ptr[name] = self.bufs[name].ptr
+        self.s, self.hs, self.host = vel_log_struct(log, ptr)
+        self.epochs = self.s.epochs
+        self.batch = int(np.asarray(log["gyro"]).shape[1])
 
-        def up(name, arr, dtype):
-            b = DeviceBuffer(np.ascontiguousarray(arr, dtype=dtype), device)
-            self.bufs[name] = b
-            return b.ptr
 
-        s.flags = up("flags", log["flags"], np.uint32)
-        s.gyro = up("gyro", log["gyro"], np.float64)
-        s.efforts = up("efforts", log["efforts"], np.float64)
-        s.dvl_index = up("dvl_index", log["dvl_index"], np.int32)
-        s.dvl = up("dvl", log["dvl"], np.float64)
-        abi.fill(s.dvl_cov, np.asarray(log["dvl_cov"]).ravel())
-        s.pressure_index = up("pressure_index", log["pressure_index"], np.int32)
-        s.pressure = up("pressure", log["pressure"], np.float64)
-        s.pressure_cov = float(log["pressure_cov"])
-        self.s = s
-        self.epochs = s.epochs
+def vel_log_check(log, first=0, count=None):
+    """uwvk_vel_log_check (host only, no device) of a DeviceVelLog, or of a host
+    log in synth.make_vel_log's layout (its arrays stand in for the device ones:
+    the check never reads through them) -> the status code."""
+    if isinstance(log, DeviceVelLog):
+        s, hs = log.s, log.hs
+    else:
+        arrays = {k: _f64(log[k]) for k in ("gyro", "efforts", "dvl", "pressure")}
+        s, hs, keep = vel_log_struct(log, {k: _p(v) for k, v in arrays.items()})
+        s.flags, s.dvl_index, s.pressure_index = hs.flags, hs.dvl_index, hs.pressure_index
+    count = s.epochs - first if count is None else count
+    return int(lib().uwvk_vel_log_check(C.byref(s), C.byref(hs), C.c_int64(first), C.c_int64(count)))
+
+
+class VelTrack:
+    """The records of one VelocityUKFBatch.run_log_track call, in device memory.
+    epochs: the absolute record epochs.  mean() / variance() / model() /
+    applied() copy to the host, ordered on the filter's stream (None for an
+    output not recorded)."""
+
+    def __init__(self, filt, epochs, bufs):
+        self.epochs = epochs
+        self.bufs = bufs
+        self._stream = filt.stream
+        self._batch = filt.batch
+        self._widths = dict(mean=4, variance=4, model=13)
+
+    def _read(self, name):
+        b = self.bufs[name]
+        shape = (len(self.epochs), self._batch, self._widths[name])
+        if b is None or not len(self.epochs):
+            return None if b is None else np.empty(shape)
+        return b.read(np.float64, shape, self._stream)
+
+    def mean(self):
+        """[records][batch][4]"""
+        return self._read("mean")
+
+    def variance(self):
+        """[records][batch][4]: the diagonal of Sigma"""
+        return self._read("variance")
+
+    def model(self):
+        """[records][batch][13]: get_state(model=True)'s motion-model state"""
+        return self._read("model")
+
+    def applied(self):
+        """[batch][2]: the DVL and pressure updates the call did not skip"""
+        b = self.bufs["applied"]
+        return None if b is None else b.read(np.uint32, (self._batch, 2), self._stream)
 
 
 class RcclComm:

@@ -2,8 +2,9 @@
 """Per-kernel ISA comparison of one translation unit between the working tree
 and a git revision: both are compiled to gfx950 assembly with the Makefile's
 flags (tools/isa_hash.py), split into functions (label .. .Lfunc_end) and
-hashed per mangled name (and their opcode sequences compared, which a
-register renaming leaves equal), so that a refactor that also ADDS kernels to a unit
+hashed per mangled name with the function index taken out of the block labels
+(and their opcode sequences compared, which a register renaming leaves
+equal), so that a refactor that also ADDS kernels to a unit
 can be shown to leave the existing kernels' code unchanged.
 
 usage: tools/kernel_isa_diff.py REV [TU ...]   (default TU: uwvk_psp_k uwvk_psp_k_r)
@@ -28,7 +29,10 @@ def kernels(pkg, tu):
     if r.returncode != 0:
         raise SystemExit(r.stderr[-2000:])
     out, ops, cur, body = {}, {}, None, []
-    for line in norm(r.stdout).splitlines():
+    # block labels carry the function's index in the unit (.LBB<function>_<block>):
+    # a kernel added in front of another renumbers them without changing its code
+    asm = re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", norm(r.stdout))
+    for line in asm.splitlines():
         m = re.match(r"^(_Z\w+):\s*$", line)
         if m:
             cur, body = m.group(1), []
