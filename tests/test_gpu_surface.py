@@ -255,7 +255,9 @@ def test_general_process_noise(eng, orc, dof, path, variant):
 def test_process_noise_imu_in_body_single_predict(eng, orc, path):
     """setProcessNoiseFromConfig with a non-identity q_imu_in_body (PoseUKF.cpp:
     410-412 rotate the bias blocks), then ONE predictionStep right away (the
-    advisor's r01 finding: the first predict must see the new Q shape)."""
+    advisor's r01 finding: the first predict must see the new Q shape).
+    The default config's blocks are isotropic, so the rotation is the identity
+    on them; tests/test_gpu_pose_config.py runs a config on which it has teeth."""
     B = 4
     cfg, uwv, log = pose_setup(B, 53, "C3", 10)
     qb = np.array([np.cos(0.3), np.sin(0.3) * 0.6, 0.0, np.sin(0.3) * 0.8])
