@@ -59,7 +59,8 @@ extern "C" {
  *      uwvk_vel_get_status; uwvk_ipose_log, uwvk_ipose_track,
  *      uwvk_ipose_log_check, uwvk_ipose_run_log, uwvk_ipose_synchronize;
  *      uwvk_vel_log_host, uwvk_vel_track, uwvk_vel_log_check,
- *      uwvk_vel_run_log_track. */
+ *      uwvk_vel_run_log_track; uwvk_pose_visual, uwvk_pose_visual_check,
+ *      uwvk_pose_run_log_visual. */
 #define UWVK_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
@@ -557,6 +558,79 @@ uwvk_status uwvk_pose_run_log_delayed(uwvk_pose* h, const uwvk_pose_log* log,
                                       const uwvk_pose_delayed* delayed /* nullable */,
                                       int64_t first, int64_t count, uint32_t* accept_counts,
                                       const uwvk_pose_track* track /* nullable */);
+
+/* Visual-landmark observations (uwvk_pose_update_visual_landmark,
+ * PoseUKF.cpp:613-654) as events of a device-resident run.  The rows are laid
+ * out as the visual part of uwvk_ipose_log: epoch e integrates the rows
+ * visual_offset[e] .. visual_offset[e+1]-1, in that order, after the epoch's
+ * delayed XY update and before its latches. */
+typedef struct uwvk_pose_visual {
+  const int64_t* visual_offset;    /* HOST [log->epochs + 1], non-decreasing (CSR); NULL only if n_visual == 0 */
+  int64_t n_visual;                /* visual rows */
+  int32_t n_features;              /* features of every row, >= 1 if a row is used */
+  const double* features;          /* DEVICE [n_visual][batch][n_features][2] */
+  const double* feature_cov;       /* DEVICE [n_visual][batch][n_features][4], NULL = shared_feature_cov */
+  const double* shared_feature_cov;/* HOST [n_features][4], serves every row */
+  const double* feature_positions; /* HOST [n_features][3] */
+  const double* marker_pose;       /* DEVICE [n_visual][batch][7], NULL = shared_marker_pose */
+  const double* shared_marker_pose;/* HOST [n_visual][7], one per row */
+  double cov_marker_pose[36];      /* host, shared */
+  double camera[4];                /* host, shared: fx, fy, cx, cy */
+  double camera_in_imu[7];         /* host, shared */
+  uint32_t* applied;               /* DEVICE [batch], nullable, caller zeroes: the rows that changed the
+                                      instance are added to it */
+} uwvk_pose_visual;
+
+/* host only, no device needed: the checks uwvk_pose_run_log_visual makes on its
+ * visual argument before it queues anything, over epochs [first, first + count)
+ * of a log of `epochs` epochs and their visual rows (the rules of
+ * uwvk_ipose_log_check for the same fields).
+ * UWVK_EINVAL: visual NULL; a negative range or one past `epochs`; n_visual < 0,
+ * or visual_offset NULL while n_visual != 0; a visual_offset entry of the range
+ * that is negative, above n_visual or below its predecessor; and, if the range
+ * holds a visual row: n_features < 1; features or feature_positions NULL;
+ * feature_cov and shared_feature_cov both NULL; marker_pose and
+ * shared_marker_pose both NULL.
+ * UWVK_ENAN: if the range holds a visual row, a non-finite value among
+ * shared_feature_cov (when feature_cov is NULL), feature_positions, the range's
+ * rows of shared_marker_pose (when marker_pose is NULL), cov_marker_pose,
+ * camera, camera_in_imu. */
+uwvk_status uwvk_pose_visual_check(const uwvk_pose_visual* visual, int64_t epochs, int64_t first, int64_t count);
+
+/* uwvk_pose_run_log_delayed (fixes and delayed may be NULL) with visual rows.
+ * visual == NULL is uwvk_pose_run_log_delayed.  Order within an epoch: predict,
+ * Acceleration, DVL, pressure, ADCP cells, BodyEfforts, XY, Z, Geographic,
+ * delayed XY, the epoch's visual rows in row order, the latches of that epoch,
+ * then a track record.  One launch per visual epoch runs all of its rows with
+ * the augmented (mu, Sigma) resident in LDS.
+ *
+ * The result is bitwise that of uwvk_pose_run_log_delayed cut after every epoch
+ * with a visual row, with at each cut one uwvk_pose_update_visual_landmark per
+ * row of that epoch, called with that row's payload, mask = the instances whose
+ * payload of that row is finite, and the shared arrays passed as shared: the
+ * final mu and Sigma, every track record, all accept-count arrays, `latched`,
+ * the status words, and the kernel choice of later calls (a visual epoch ends
+ * the parameter-decoupled kernels, as the single call does).  Calls over
+ * adjacent ranges give bitwise what one call over the whole range gives.
+ *
+ * The payloads are in device memory, so what the single call refuses on the
+ * host is handled per instance, as by uwvk_ipose_run_log:
+ *  - a non-finite feature, feature covariance or per-instance marker pose of an
+ *    instance at a row: that row is skipped for that instance, UWVK_ST_NAN;
+ *  - a row in which any feature's update fails (at the sigma spread or in
+ *    apply_delta's re-spread) is discarded for that instance as a whole:
+ *    (mu, Sigma) as before the row, UWVK_ST_NOTPD, later rows and epochs run.
+ *
+ * Returns uwvk_pose_visual_check(visual, log->epochs, first, count) first (h or
+ * log NULL: UWVK_EINVAL), then the errors of uwvk_pose_run_log_delayed, all
+ * with nothing queued and the state untouched.  Asynchronous on the handle's
+ * stream like the other runs: the host arrays are copied before it returns. */
+uwvk_status uwvk_pose_run_log_visual(uwvk_pose* h, const uwvk_pose_log* log,
+                                     const uwvk_pose_fixes* fixes /* nullable */,
+                                     const uwvk_pose_delayed* delayed /* nullable */,
+                                     const uwvk_pose_visual* visual /* nullable */,
+                                     int64_t first, int64_t count, uint32_t* accept_counts,
+                                     const uwvk_pose_track* track /* nullable */);
 
 /* Ensemble statistics over the batch (for Monte-Carlo runs):
  * out[0..store)        = sum_i x_i (orientation quaternion summed componentwise)

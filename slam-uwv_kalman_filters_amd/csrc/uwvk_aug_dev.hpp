@@ -33,6 +33,9 @@ struct Seg {
   static constexpr int store = K == SEG_V ? D : (K == SEG_S2 ? 3 : 4);
 };
 
+// device-side screening of the run kernels (k_bottom_run, k_ipose_run, k_pose_visual_run)
+UWVK_DEV bool finite_dev(double v) { return v - v == 0.0; }  // neither NaN nor Inf
+
 // ---- S2 [EXT MTK S2], DESIGN.md §3 item 11 ---------------------------------
 // R_x = minimal rotation e3 -> x, columns (b1, b2, x)
 UWVK_DEV void s2_basis(const double x[3], double b1[3], double b2[3]) {
@@ -445,6 +448,18 @@ struct VisArgs {             // device pointers
   double cov_marker[36];
   double cam[4];             // fx, fy, cx, cy (CameraConfiguration, PoseUKFConfig.hpp:125-131)
   double cam_in[7];          // camera in body / IMU, t(3) q(4)
+};
+
+// One VISUAL launch of uwvk_pose_run_log_visual (k_pose_visual_run): rows
+// [row, row + rows) of the caller's device arrays, all of one epoch.
+constexpr int kVisRunRows = 64;  // rows per launch (the kernel's skip mask)
+struct VisRunArgs {
+  VisArgs va;                 // features, fcov, marker: row 0 of the arrays; ref, mask unused
+  int64_t row;                // first row of this launch
+  int32_t rows;               // <= kVisRunRows
+  const double* marker_rows;  // DEVICE shared marker poses [rows of the call][7], or NULL (per instance)
+  int64_t row_base;           // the visual row that marker_rows starts at
+  uint32_t* applied;          // [batch], nullable
 };
 
 // measurementVisualLandmark: ((body_in_nav [* pose_error]) * cam_in_body)^-1 *

@@ -4,8 +4,8 @@
 // fixes, latches and track records), the checks of the fix and delayed
 // arguments, the grid and tail layout of one launch, and the process-noise
 // tables.  uwvk_pose.hip does the copies and walks the list;
-// tests/cpp/plan_test.cpp, track_plan_test.cpp, fix_plan_test.cpp and
-// delayed_plan_test.cpp check this file on the CPU.
+// tests/cpp/plan_test.cpp, track_plan_test.cpp, fix_plan_test.cpp,
+// delayed_plan_test.cpp and visual_plan_test.cpp check this file on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -153,7 +153,7 @@ inline bool runs_pair(const EpochFacts& f) {
   return f.dof == 26 ? f.q_simple : runs_pd(f);
 }
 
-enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EPOCH_DENSE, EFFORTS, FIX, LATCH, RECORD };
+enum LaunchKind { EPOCH_ONE, EPOCH_PAIR, EPOCH_DENSE, EFFORTS, FIX, LATCH, RECORD, VISUAL };
 struct Launch {
   LaunchKind kind;
   int64_t first, count;  // absolute epochs [first, first + count); all but EPOCH_ONE / EPOCH_PAIR: the one epoch
@@ -237,23 +237,28 @@ constexpr uint32_t kDelayedLatch = 0x10u;  // rows latch the position after this
 
 // The launch list of one run_log call, in stream order.  One rule: the range
 // [first, first + count) is cut after every epoch with an event (a fix flag,
-// an arrival, a latch, or a track record: (e + 1) % every == 0); each piece is
+// an arrival, a visual row, a latch, or a track record: (e + 1) % every == 0); each piece is
 // planned by plan_epochs on its own, pdec carried from piece to piece; then the
 // epoch's events follow the piece (and its EFFORTS launch, if the epoch has
 // one) in the order of uwvk.h: one FIX launch if the epoch has fixes or an
 // arrival (ev_any the UWVK_FIX_* kinds plus kDelayedArrive: the delayed update
-// is the last position update, in the same launch), one LATCH (the latch sees
-// all updates of its epoch), one RECORD.  So a call with events is the calls
+// is the last position update, in the same launch), one VISUAL launch if the
+// epoch has visual-landmark rows (uwvk_pose_run_log_visual: all of its rows, in
+// row order), one LATCH (the latch sees all updates of its epoch), one RECORD.  So a call with events is the calls
 // of its pieces, launch for launch, and without events it is plan_epochs' plan.
 // The position updates are linear in the position rows and leave the
-// parameter block decoupled: pd / pair go on after them.
+// parameter block decoupled: pd / pair go on after them.  The visual update is
+// the literal augmented one (all sigma points), as the single call: pdec is
+// false after a VISUAL launch and the later pieces run the general kernel.
 // A dense handle (the literal kernels) runs one fused EPOCH_DENSE launch per
 // epoch instead, its efforts update included (no EFFORTS launch; host_flags is
 // not read), and is never parameter-decoupled afterwards.
-// host_flags, fix_flags, delayed_flags: those of epochs first .. first + count
-// - 1, the last two or null (none); every: the track's stride, or 0 (no track)
+// host_flags, fix_flags, delayed_flags, visual_flags: those of epochs first ..
+// first + count - 1, the last three or null (none); visual_flags[k] != 0: epoch
+// first + k has a visual row; every: the track's stride, or 0 (no track)
 inline EpochPlan plan_run(const uint32_t* host_flags, const uint32_t* fix_flags, const uint32_t* delayed_flags,
-                          int64_t every, int64_t first, int64_t count, EpochFacts f) {
+                          int64_t every, int64_t first, int64_t count, EpochFacts f,
+                          const uint32_t* visual_flags = nullptr) {
   EpochPlan p;
   if (f.dense) f.pdec = false;
   p.pdec = f.pdec;
@@ -261,9 +266,10 @@ inline EpochPlan plan_run(const uint32_t* host_flags, const uint32_t* fix_flags,
   auto fixes = [&](int64_t k) { return fix_flags ? fix_flags[k - first] : 0u; };
   auto delayed = [&](int64_t k) { return delayed_flags ? delayed_flags[k - first] & (kDelayedArrive | kDelayedLatch) : 0u; };
   auto record = [&](int64_t k) { return every > 0 && (k + 1) % every == 0; };
+  auto visual = [&](int64_t k) { return visual_flags && visual_flags[k - first] != 0u; };
   for (int64_t e = first; e < end;) {
     int64_t stop = e;
-    while (stop < end && !(fixes(stop) || delayed(stop) || record(stop))) stop++;
+    while (stop < end && !(fixes(stop) || delayed(stop) || visual(stop) || record(stop))) stop++;
     const bool event = stop < end;
     if (event) stop++;  // the piece includes its event epoch
     if (f.dense) {
@@ -277,6 +283,10 @@ inline EpochPlan plan_run(const uint32_t* host_flags, const uint32_t* fix_flags,
       const int64_t k = stop - 1;
       const uint32_t fix = fixes(k) | (delayed(k) & kDelayedArrive);
       if (fix) p.launches.push_back({FIX, k, 1, 0, 0, fix});
+      if (visual(k)) {
+        p.launches.push_back({VISUAL, k, 1, 0, 0, 0});
+        f.pdec = p.pdec = false;
+      }
       if (delayed(k) & kDelayedLatch) p.launches.push_back({LATCH, k, 1, 0, 0, kDelayedLatch});
       if (record(k)) p.launches.push_back({RECORD, k, 1, 0, 0, 0});
     }

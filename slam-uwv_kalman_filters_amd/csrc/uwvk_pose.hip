@@ -11,9 +11,11 @@
 #include "uwvk_track.hpp"
 #include "uwvk_host.hpp"
 #include "uwvk_aug_dev.hpp"
+#include "uwvk_stage.hpp"
 
 namespace uwvk {
 hipError_t launch_pose_visual(int dof, int right, hipStream_t st, const PoseBufs& b, const aug::VisArgs& va);
+hipError_t launch_pose_visual_run(int dof, int right, hipStream_t st, const PoseBufs& b, const aug::VisRunArgs& a);
 }
 
 #include <algorithm>
@@ -82,6 +84,7 @@ struct uwvk_pose {
   uint32_t ticket_next = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   aug::VisStage vis;  // visual-landmark update staging
+  std::vector<StageSlot> stages;  // uwvk_pose_run_log_visual: the shared visual inputs of a call
 };
 
 // literal (all 2n+1 sigma points) kernels requested?
@@ -229,6 +232,7 @@ void uwvk_pose_destroy(uwvk_pose* h) {
     if (p) (void)hipFree(p);
   if (h->h_fault) (void)hipHostFree(h->h_fault);
   h->vis.release();
+  stage_release(h->stages);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -740,14 +744,62 @@ int64_t uwvk_pose_track_records(int64_t first, int64_t count, int64_t every) {
   return first < 0 || count < 0 || every <= 0 ? 0 : track_records(first, count, every);
 }
 
-// The four uwvk_pose_run_log* entry points: track, fx and dly are each null or
-// that call's argument.  After the argument checks (fixes_valid and
-// delayed_events, uwvk_plan.hpp) the whole call is planned once by plan_run
-// and its launches are queued on the handle's stream in the plan's order.
+// host only (no HIP call): what uwvk_pose_run_log_visual checks of its visual
+// argument before it queues anything (the rules of uwvk_ipose_log_check)
+uwvk_status uwvk_pose_visual_check(const uwvk_pose_visual* v, int64_t epochs, int64_t first, int64_t count) {
+  if (!v || epochs < 0 || first < 0 || count < 0 || first > epochs || count > epochs - first) return UWVK_EINVAL;
+  if (v->n_visual < 0 || (!v->visual_offset && v->n_visual != 0)) return UWVK_EINVAL;
+  int64_t row0 = 0, row1 = 0;
+  if (v->visual_offset) {
+    for (int64_t e = first; e <= first + count; e++) {
+      const int64_t o = v->visual_offset[e];
+      if (o < 0 || o > v->n_visual || (e > first && o < v->visual_offset[e - 1])) return UWVK_EINVAL;
+    }
+    row0 = v->visual_offset[first];
+    row1 = v->visual_offset[first + count];
+  }
+  if (row1 <= row0) return UWVK_OK;
+  if (v->n_features < 1 || !v->features || !v->feature_positions) return UWVK_EINVAL;
+  if ((!v->feature_cov && !v->shared_feature_cov) || (!v->marker_pose && !v->shared_marker_pose)) return UWVK_EINVAL;
+  // the shared host values the range uses (checkMeasurment of the single call)
+  const size_t nf = (size_t)v->n_features;
+  if (!v->feature_cov && !finite_all(v->shared_feature_cov, nf * 4)) return UWVK_ENAN;
+  if (!finite_all(v->feature_positions, nf * 3)) return UWVK_ENAN;
+  if (!v->marker_pose && !finite_all(v->shared_marker_pose + row0 * 7, (size_t)(row1 - row0) * 7)) return UWVK_ENAN;
+  if (!finite_all(v->cov_marker_pose, 36) || !finite_all(v->camera, 4) || !finite_all(v->camera_in_imu, 7))
+    return UWVK_ENAN;
+  return UWVK_OK;
+}
+
+// VISUAL: the rows of epoch e in one launch (kVisRunRows at most per launch;
+// the state's round trip through HBM between two launches is exact)
+static hipError_t visual_epoch_rows(uwvk_pose* h, const PoseBufs& b, const uwvk_pose_visual* vis, aug::VisRunArgs a,
+                                    int64_t e) {
+  const int64_t r0 = vis->visual_offset[e], r1 = vis->visual_offset[e + 1];
+  hipError_t le = hipSuccess;
+  for (int64_t r = r0; r < r1 && le == hipSuccess; r += aug::kVisRunRows) {
+    a.row = r;
+    a.rows = (int32_t)std::min<int64_t>(aug::kVisRunRows, r1 - r);
+    le = launch_pose_visual_run(h->dof, h->sh.so3_right, h->stream, b, a);
+  }
+  return le;
+}
+
+// The five uwvk_pose_run_log* entry points: track, fx, dly and vis are each
+// null or that call's argument.  After the argument checks
+// (uwvk_pose_visual_check; fixes_valid and delayed_events, uwvk_plan.hpp) the
+// whole call is planned once by plan_run and its launches are queued on the
+// handle's stream in the plan's order.
 static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first, int64_t count,
                            uint32_t* accept_counts, const uwvk_pose_track* track,
-                           const uwvk_pose_fixes* fx = nullptr, const uwvk_pose_delayed* dly = nullptr) {
-  if (!h || !log || first < 0 || count < 0 || first + count > log->epochs || log->adcp_cells > 8) return UWVK_EINVAL;
+                           const uwvk_pose_fixes* fx = nullptr, const uwvk_pose_delayed* dly = nullptr,
+                           const uwvk_pose_visual* vis = nullptr) {
+  if (!h || !log) return UWVK_EINVAL;
+  if (vis) {
+    const uwvk_status chk = uwvk_pose_visual_check(vis, log->epochs, first, count);
+    if (chk != UWVK_OK) return chk;
+  }
+  if (first < 0 || count < 0 || first + count > log->epochs || log->adcp_cells > 8) return UWVK_EINVAL;
   if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->stats) ||
                 track->capacity < track_records(first, count, track->every)))
     return UWVK_EINVAL;
@@ -792,8 +844,59 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
     ea.efforts_only = 0;
   }
   const PoseShared sh = h->sh;  // after upload_shared (it refreshes the Q shape)
+  // the visual rows of the range: the per-epoch flags of the plan, and the
+  // shared host inputs of all of the call's rows staged once (feature
+  // positions, shared feature covariance, the rows' shared marker poses)
+  std::vector<uint32_t> vfl;
+  aug::VisRunArgs vra{};
+  StageSlot* sg = nullptr;
+  const int64_t vrow0 = vis && vis->visual_offset ? vis->visual_offset[first] : 0;
+  const int64_t vrows = vis && vis->visual_offset ? vis->visual_offset[first + count] - vrow0 : 0;
+  if (vrows > 0) {
+    vfl.resize((size_t)count);
+    for (int64_t k = 0; k < count; k++)
+      vfl[(size_t)k] = vis->visual_offset[first + k + 1] > vis->visual_offset[first + k] ? 1u : 0u;
+    const size_t nf = (size_t)vis->n_features;
+    const size_t w_pos = nf * 3, w_cov = vis->feature_cov ? 0 : nf * 4,
+                 w_mk = vis->marker_pose ? 0 : (size_t)vrows * 7, w_all = w_pos + w_cov + w_mk;
+    sg = stage_acquire(h->stages, w_all * 8);
+    if (!sg) return UWVK_ENOMEM;
+    double* hw = (double*)sg->host;
+    const double* dw = (const double*)sg->dev;
+    std::memcpy(hw, vis->feature_positions, w_pos * 8);
+    if (w_cov) std::memcpy(hw + w_pos, vis->shared_feature_cov, w_cov * 8);
+    if (w_mk) std::memcpy(hw + w_pos + w_cov, vis->shared_marker_pose + vrow0 * 7, w_mk * 8);
+    HIPCHK(hipMemcpyAsync(sg->dev, sg->host, w_all * 8, hipMemcpyHostToDevice, h->stream));
+    sg->used = true;
+    vra.va.nf = vis->n_features;
+    vra.va.features = vis->features;
+    vra.va.fcov = vis->feature_cov ? vis->feature_cov : dw + w_pos;
+    vra.va.fcov_stride = vis->feature_cov ? (int64_t)nf * 4 : 0;
+    vra.va.fpos = dw;
+    vra.va.marker = vis->marker_pose;
+    vra.va.marker_stride = vis->marker_pose ? 7 : 0;
+    std::memcpy(vra.va.cov_marker, vis->cov_marker_pose, sizeof(vra.va.cov_marker));
+    std::memcpy(vra.va.cam, vis->camera, sizeof(vra.va.cam));
+    std::memcpy(vra.va.cam_in, vis->camera_in_imu, sizeof(vra.va.cam_in));
+    vra.marker_rows = w_mk ? dw + w_pos + w_cov : nullptr;
+    vra.row_base = vrow0;
+    vra.applied = vis->applied;
+  }
   const EpochPlan plan = plan_run(hf, fx ? fx->host_flags + first : nullptr, dly ? events.flags.data() : nullptr,
-                                  track ? track->every : 0, first, count, facts(h));
+                                  track ? track->every : 0, first, count, facts(h), vrows > 0 ? vfl.data() : nullptr);
+  // the slot is free again once the launches queued so far have passed: the
+  // event is recorded when this function returns, an early return after a
+  // failed launch included (a return before `used` is set leaves the slot free)
+  struct SlotDone {
+    StageSlot* sg;
+    hipStream_t st;
+    ~SlotDone() {
+      if (sg && sg->used && hipEventRecord(sg->done, st) != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        sg->used = false;
+      }
+    }
+  } slot_done{sg, h->stream};
   const int s = h->store, nout = 3 * s + 2;
   int64_t r = 0;  // the next record of this call
   for (const Launch& l : plan.launches) {
@@ -816,6 +919,10 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
         break;
       case FIX:  // the position updates leave pdec as it is
         HIPCHK(use_dense(h) ? fix_dense(h, b, sh, fx, dly, l.first, l.ev_any) : fix_psp(h, b, sh, fx, dly, l.first, l.ev_any));
+        break;
+      case VISUAL:  // the literal augmented update (all sigma points), as the single call
+        h->pdec = false;
+        HIPCHK(visual_epoch_rows(h, b, vis, vra, l.first));
         break;
       case LATCH:
         HIPCHK(latch_epoch_rows(h, events, dly->latched, l.first));
@@ -859,6 +966,13 @@ uwvk_status uwvk_pose_run_log_delayed(uwvk_pose* h, const uwvk_pose_log* log, co
                                       uint32_t* accept_counts, const uwvk_pose_track* track) {
   UWVK_DEVICE_GUARD(h);
   return run_log(h, log, first, count, accept_counts, track, fixes, delayed);
+}
+
+uwvk_status uwvk_pose_run_log_visual(uwvk_pose* h, const uwvk_pose_log* log, const uwvk_pose_fixes* fixes,
+                                     const uwvk_pose_delayed* delayed, const uwvk_pose_visual* visual, int64_t first,
+                                     int64_t count, uint32_t* accept_counts, const uwvk_pose_track* track) {
+  UWVK_DEVICE_GUARD(h);
+  return run_log(h, log, first, count, accept_counts, track, fixes, delayed, visual);
 }
 
 uwvk_status uwvk_pose_ensemble_stats(uwvk_pose* h, const double* truth, double* out) {

@@ -16,6 +16,7 @@
 #include "uwvk_aug_dev.hpp"
 #include "../../include/uwvk.h"
 #include "uwvk_host.hpp"
+#include "uwvk_stage.hpp"
 
 using namespace uwvk;
 using namespace uwvk::aug;
@@ -203,7 +204,6 @@ struct BottomRunArgs {
   M9 Q;
 };
 
-UWVK_DEV bool finite_dev(double v) { return v - v == 0.0; }  // neither NaN nor Inf
 
 __global__ __launch_bounds__(BE::BLOCK) void k_bottom_run(SmallBufs b, BottomRunArgs a) {
   __shared__ double smem[BE::IPB * BE::words];
@@ -583,61 +583,7 @@ struct SmallHandle {
   SmallBufs bufs() const { return SmallBufs{batch, d_mu, d_sigma, d_status}; }
 };
 
-// The host arrays of one uwvk_bottom_run_log / uwvk_ipose_run_log call (the
-// epoch table; for IndirectPoseUKF the shared visual inputs before it): written
-// into pinned host memory before the call returns, copied to the device on the
-// handle's stream.  A slot is free again once the event behind its last launch
-// has passed.
-struct StageSlot {
-  char* host = nullptr;  // pinned
-  char* dev = nullptr;
-  size_t cap = 0;        // bytes
-  hipEvent_t done = nullptr;
-  bool used = false;
-};
-
-static void stage_release(std::vector<StageSlot>& stages) {
-  for (StageSlot& s : stages) {
-    if (s.host) (void)hipHostFree(s.host);
-    if (s.dev) (void)hipFree(s.dev);
-    if (s.done) (void)hipEventDestroy(s.done);
-  }
-  stages.clear();
-}
-
-// a slot of at least `bytes` that no queued launch reads any more
-static StageSlot* stage_acquire(std::vector<StageSlot>& stages, size_t bytes) {
-  StageSlot* s = nullptr;
-  for (StageSlot& c : stages)
-    if (!c.used || hipEventQuery(c.done) == hipSuccess) {
-      c.used = false;
-      if (!s) s = &c;
-    }
-  if (!s) {
-    stages.emplace_back();
-    s = &stages.back();
-    if (hipEventCreateWithFlags(&s->done, hipEventDisableTiming) != hipSuccess) {
-      s->done = nullptr;
-      stages.pop_back();
-      return nullptr;
-    }
-  }
-  if (s->cap < bytes) {
-    if (s->host) (void)hipHostFree(s->host);
-    if (s->dev) (void)hipFree(s->dev);
-    s->host = s->dev = nullptr;
-    s->cap = 0;
-    const size_t cap = std::max<size_t>(bytes, 32768);
-    if (hipHostMalloc((void**)&s->host, cap, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void**)&s->dev, cap) != hipSuccess) {
-      if (s->host) (void)hipHostFree(s->host);
-      s->host = s->dev = nullptr;
-      return nullptr;
-    }
-    s->cap = cap;
-  }
-  return s;
-}
+// StageSlot, stage_acquire, stage_release: the host arrays of one run call (uwvk_stage.hpp)
 
 struct uwvk_bottom : SmallHandle {
   M9 Q{};

@@ -596,6 +596,17 @@ class PoseUKF {
                      const uwvk_pose_track* track = nullptr) {
     check(uwvk_pose_run_log_delayed(h_, &log, fixes, &delayed, first, count, accept_counts, track), "runLogDelayed");
   }
+  // runLogDelayed (fixes and delayed nullable) with visual-landmark rows
+  // (uwvk_pose_run_log_visual): the rows of `visual` are integrated at their
+  // epochs, after that epoch's delayed update and before its latches, one
+  // launch per visual epoch; the payloads stay in device memory and a
+  // non-finite one skips that row for that instance only (UWVK_ST_NAN).
+  void runLogVisual(const uwvk_pose_log& log, const uwvk_pose_fixes* fixes, const uwvk_pose_delayed* delayed,
+                    const uwvk_pose_visual& visual, int64_t first, int64_t count, uint32_t* accept_counts = nullptr,
+                    const uwvk_pose_track* track = nullptr) {
+    check(uwvk_pose_run_log_visual(h_, &log, fixes, delayed, &visual, first, count, accept_counts, track),
+          "runLogVisual");
+  }
   void synchronize() { check(uwvk_pose_synchronize(h_), "synchronize"); }
 
  private:

@@ -91,6 +91,13 @@ class PoseDelayed(C.Structure):  # uwvk_pose_delayed (index arrays host, payload
                 ("latched", P), ("accept_counts", P)]
 
 
+class PoseVisual(C.Structure):  # uwvk_pose_visual (offsets / shared inputs host, payloads device)
+    _fields_ = [("visual_offset", P), ("n_visual", C.c_int64), ("n_features", C.c_int32), ("features", P),
+                ("feature_cov", P), ("shared_feature_cov", P), ("feature_positions", P), ("marker_pose", P),
+                ("shared_marker_pose", P), ("cov_marker_pose", _arr(D, 36)), ("camera", _arr(D, 4)),
+                ("camera_in_imu", _arr(D, 7)), ("applied", P)]
+
+
 class VelLog(C.Structure):  # uwvk_vel_log (device pointers)
     _fields_ = [("epochs", C.c_int64), ("dt", D), ("flags", P), ("gyro", P), ("efforts", P),
                 ("dvl_index", P), ("dvl", P), ("dvl_cov", _arr(D, 9)),

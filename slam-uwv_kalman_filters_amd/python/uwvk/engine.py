@@ -52,6 +52,7 @@ SYMBOLS = [
     "uwvk_bottom_log_check", "uwvk_bottom_run_log", "uwvk_bottom_synchronize",
     "uwvk_ipose_log_check", "uwvk_ipose_run_log", "uwvk_ipose_synchronize",
     "uwvk_vel_log_check", "uwvk_vel_run_log_track",
+    "uwvk_pose_visual_check", "uwvk_pose_run_log_visual",
 ]
 
 _LIB = None
@@ -353,14 +354,26 @@ class PoseUKFBatch:
     def upload_delayed(self, delayed, counts=False):
         return DevicePoseDelayed(delayed, self.batch, self.device, counts)
 
-    def run_log(self, dlog, first=0, count=None, accept_counts=None, sync=True, fixes=None, delayed=None):
+    def upload_visual(self, visual, counts=False):
+        return DevicePoseVisual(visual, self.batch, self.device, counts)
+
+    def _run_log_visual(self, dlog, fixes, delayed, visual, first, count, ac, tr):
+        _chk(self.L.uwvk_pose_run_log_visual(self.h, C.byref(dlog.s), C.byref(fixes.s) if fixes is not None else None,
+                                             C.byref(delayed.s) if delayed is not None else None, C.byref(visual.s),
+                                             C.c_int64(first), C.c_int64(count), ac, tr), "run_log_visual")
+
+    def run_log(self, dlog, first=0, count=None, accept_counts=None, sync=True, fixes=None, delayed=None,
+                visual=None):
         """Queue epochs [first, first+count) on the handle's stream (PSP: one
         launch per run of epochs without BodyEfforts); sync=False leaves them in flight.
         fixes: a DevicePoseFixes, the position fixes of the log (uwvk_pose_run_log_fixes).
-        delayed: a DevicePoseDelayed, its delayed XY rows (uwvk_pose_run_log_delayed)."""
+        delayed: a DevicePoseDelayed, its delayed XY rows (uwvk_pose_run_log_delayed).
+        visual: a DevicePoseVisual, its visual-landmark rows (uwvk_pose_run_log_visual)."""
         count = dlog.epochs - first if count is None else count
         ac = accept_counts.ptr if accept_counts is not None else None
-        if delayed is not None:
+        if visual is not None:
+            self._run_log_visual(dlog, fixes, delayed, visual, first, count, ac, None)
+        elif delayed is not None:
             _chk(self.L.uwvk_pose_run_log_delayed(self.h, C.byref(dlog.s), C.byref(fixes.s) if fixes is not None else None,
                                                   C.byref(delayed.s), C.c_int64(first), C.c_int64(count), ac, None),
                  "run_log_delayed")
@@ -377,7 +390,7 @@ class PoseUKFBatch:
         return int(self.L.uwvk_pose_track_records(first, count, every))
 
     def run_log_track(self, dlog, every, first=0, count=None, accept_counts=None, mean=True, variance=True,
-                      stats=False, truth=None, sync=True, capacity=None, fixes=None, delayed=None):
+                      stats=False, truth=None, sync=True, capacity=None, fixes=None, delayed=None, visual=None):
         """run_log with a record of all instances after every absolute epoch e
         with (e + 1) % every == 0 (uwvk_pose_run_log_track): the means, the
         diagonal of Sigma and / or the ensemble statistics against truth
@@ -387,7 +400,8 @@ class PoseUKFBatch:
         range takes).  fixes: a DevicePoseFixes (uwvk_pose_run_log_fixes); the
         record of a fix epoch holds the state after its fixes.  delayed: a
         DevicePoseDelayed (uwvk_pose_run_log_delayed); a record follows the
-        epoch's delayed update and latches."""
+        epoch's delayed update and latches.  visual: a DevicePoseVisual
+        (uwvk_pose_run_log_visual); a record follows the epoch's visual rows."""
         count = dlog.epochs - first if count is None else count
         n = self.track_records(first, count, every)
         cap = n if capacity is None else int(capacity)
@@ -406,7 +420,9 @@ class PoseUKFBatch:
         tr.mean, tr.variance, tr.stats = (bufs[k].ptr if bufs[k] else None for k in ("mean", "variance", "stats"))
         tr.truth = _p(t)
         ac = accept_counts.ptr if accept_counts is not None else None
-        if delayed is not None:
+        if visual is not None:
+            self._run_log_visual(dlog, fixes, delayed, visual, first, count, ac, C.byref(tr))
+        elif delayed is not None:
             _chk(self.L.uwvk_pose_run_log_delayed(self.h, C.byref(dlog.s), C.byref(fixes.s) if fixes is not None else None,
                                                   C.byref(delayed.s), C.c_int64(first), C.c_int64(count), ac,
                                                   C.byref(tr)), "run_log_delayed")
@@ -607,6 +623,76 @@ class DevicePoseDelayed:
     def latched(self, stream=None):
         """[n][batch][2] the latched positions (rows not yet latched as uploaded)."""
         return self.bufs["latched"].read(np.float64, (self.n, self.batch, 2), stream)
+
+
+POSE_VISUAL_DEVICE_ARRAYS = ("features", "feature_cov", "marker_pose")
+
+
+def pose_visual_struct(visual, ptr):
+    """abi.PoseVisual of a host dict.  visual: {"visual_offset" [epochs + 1]
+    (CSR: epoch e has the rows visual_offset[e] .. visual_offset[e + 1] - 1),
+    "n_features", "features" [n][batch][nf][2], "feature_positions" [nf][3],
+    "feature_cov" [n][batch][nf][4] or "shared_feature_cov" [nf][4],
+    "marker_pose" [n][batch][7] or "shared_marker_pose" [n][7],
+    "cov_marker_pose" 6x6, "camera" (fx, fy, cx, cy), "camera_in_imu" t(3) q(4)}.
+    ptr: the addresses of its DEVICE arrays {features, feature_cov,
+    marker_pose} (None: absent).  Returns (struct, the host arrays it points
+    into: keep them alive)."""
+    s = abi.PoseVisual()
+    s.n_features = int(visual["n_features"])
+    keep = {}
+    for k, t in (("visual_offset", np.int64), ("shared_feature_cov", np.float64), ("feature_positions", np.float64),
+                 ("shared_marker_pose", np.float64)):
+        if visual.get(k) is not None:
+            keep[k] = np.ascontiguousarray(visual[k], dtype=t)
+        setattr(s, k, _p(keep.get(k)))
+    s.n_visual = int(visual["n_visual"]) if "n_visual" in visual else \
+        (0 if visual.get("features") is None else len(visual["features"]))
+    for k in POSE_VISUAL_DEVICE_ARRAYS:
+        setattr(s, k, ptr.get(k))
+    abi.fill(s.cov_marker_pose, np.asarray(visual["cov_marker_pose"], float).reshape(-1))
+    abi.fill(s.camera, np.asarray(visual["camera"], float).reshape(-1))
+    abi.fill(s.camera_in_imu, np.asarray(visual["camera_in_imu"], float).reshape(-1))
+    return s, keep
+
+
+class DevicePoseVisual:
+    """uwvk_pose_visual: the visual-landmark rows of a log.  The payloads
+    (features, feature_cov, marker_pose) live in device memory; the row offsets
+    and the shared inputs stay on the host (kept alive here).  visual: a dict in
+    pose_visual_struct's layout.  counts: allocate the [batch] applied counts
+    (zeroed).  One object may serve calls over adjacent ranges."""
+
+    def __init__(self, visual, batch, device=0, counts=False):
+        self.bufs, ptr = {}, {}
+        for name in POSE_VISUAL_DEVICE_ARRAYS:
+            if visual.get(name) is not None and np.asarray(visual[name]).size:
+                self.bufs[name] = DeviceBuffer(np.ascontiguousarray(visual[name], dtype=np.float64), device)
+                ptr[name] = self.bufs[name].ptr
+        self.s, self.host = pose_visual_struct(visual, ptr)
+        self.batch = batch
+        if counts:
+            self.bufs["applied"] = DeviceBuffer(np.zeros(batch, np.uint32), device)
+            self.s.applied = self.bufs["applied"].ptr
+
+    def applied(self, stream=None):
+        """[batch] visual rows that changed each instance so far (None without counts)."""
+        b = self.bufs.get("applied")
+        return None if b is None else b.read(np.uint32, (self.batch,), stream)
+
+
+def pose_visual_check(visual, epochs, first=0, count=None):
+    """uwvk_pose_visual_check (host only, no device) of a DevicePoseVisual, or of
+    a host dict in pose_visual_struct's layout (its arrays stand in for the
+    device ones: the check never reads through them) over epochs [first, first
+    + count) of a log of `epochs` epochs -> the status code."""
+    if isinstance(visual, DevicePoseVisual):
+        s = visual.s
+    else:
+        arrays = {k: _f64(visual[k]) for k in POSE_VISUAL_DEVICE_ARRAYS if visual.get(k) is not None}
+        s, keep = pose_visual_struct(visual, {k: _p(v) for k, v in arrays.items()})
+    count = epochs - first if count is None else count
+    return int(lib().uwvk_pose_visual_check(C.byref(s), C.c_int64(epochs), C.c_int64(first), C.c_int64(count)))
 
 
 class VelocityUKFBatch:
