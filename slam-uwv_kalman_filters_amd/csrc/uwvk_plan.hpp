@@ -2,8 +2,9 @@
 // integers and host arrays (plain C++17, no HIP): which epoch kernel a handle
 // runs, the one launch list of a call (plan_run: epochs, BodyEfforts, position
 // fixes, latches and track records), the checks of the fix and delayed
-// arguments, the grid and tail layout of one launch, and the process-noise
-// tables.  uwvk_pose.hip does the copies and walks the list;
+// arguments and of the track argument (track_args_valid, which the run_log
+// calls of the other filters share), the grid and tail layout of one launch,
+// and the process-noise tables.  uwvk_pose.hip does the copies and walks the list;
 // tests/cpp/plan_test.cpp, track_plan_test.cpp, fix_plan_test.cpp,
 // delayed_plan_test.cpp and visual_plan_test.cpp check this file on the CPU.
 #pragma once
@@ -226,6 +227,12 @@ inline EpochPlan plan_epochs(const uint32_t* host_flags, int64_t first, int64_t 
 // epoch e with (e + 1) % every == 0.  Records in [first, first + count), every > 0:
 inline int64_t track_records(int64_t first, int64_t count, int64_t every) {
   return (first + count) / every - first / every;
+}
+// The track argument of every run_log entry point (PoseUKF, BottomUKF,
+// IndirectPoseUKF, VelocityUKF), after the range check (first, count >= 0): a
+// positive stride, at least one output array, and room for the range's records.
+inline bool track_args_valid(int64_t every, int64_t capacity, bool any_output, int64_t first, int64_t count) {
+  return every > 0 && any_output && capacity >= track_records(first, count, every);
 }
 
 // Delayed XY (uwvk_pose_run_log_delayed): per epoch two internal bits, made by

@@ -12,6 +12,7 @@
 #include "uwvk_host.hpp"
 #include "uwvk_aug_dev.hpp"
 #include "uwvk_stage.hpp"
+#include "uwvk_visual_rows.hpp"
 
 namespace uwvk {
 hipError_t launch_pose_visual(int dof, int right, hipStream_t st, const PoseBufs& b, const aug::VisArgs& va);
@@ -749,25 +750,10 @@ int64_t uwvk_pose_track_records(int64_t first, int64_t count, int64_t every) {
 uwvk_status uwvk_pose_visual_check(const uwvk_pose_visual* v, int64_t epochs, int64_t first, int64_t count) {
   if (!v || epochs < 0 || first < 0 || count < 0 || first > epochs || count > epochs - first) return UWVK_EINVAL;
   if (v->n_visual < 0 || (!v->visual_offset && v->n_visual != 0)) return UWVK_EINVAL;
-  int64_t row0 = 0, row1 = 0;
-  if (v->visual_offset) {
-    for (int64_t e = first; e <= first + count; e++) {
-      const int64_t o = v->visual_offset[e];
-      if (o < 0 || o > v->n_visual || (e > first && o < v->visual_offset[e - 1])) return UWVK_EINVAL;
-    }
-    row0 = v->visual_offset[first];
-    row1 = v->visual_offset[first + count];
-  }
-  if (row1 <= row0) return UWVK_OK;
-  if (v->n_features < 1 || !v->features || !v->feature_positions) return UWVK_EINVAL;
-  if ((!v->feature_cov && !v->shared_feature_cov) || (!v->marker_pose && !v->shared_marker_pose)) return UWVK_EINVAL;
-  // the shared host values the range uses (checkMeasurment of the single call)
-  const size_t nf = (size_t)v->n_features;
-  if (!v->feature_cov && !finite_all(v->shared_feature_cov, nf * 4)) return UWVK_ENAN;
-  if (!finite_all(v->feature_positions, nf * 3)) return UWVK_ENAN;
-  if (!v->marker_pose && !finite_all(v->shared_marker_pose + row0 * 7, (size_t)(row1 - row0) * 7)) return UWVK_ENAN;
-  if (!finite_all(v->cov_marker_pose, 36) || !finite_all(v->camera, 4) || !finite_all(v->camera_in_imu, 7))
-    return UWVK_ENAN;
+  const VisualRows vr(*v);
+  int64_t row0, row1;
+  if (!visual_rows_valid(vr, first, count, &row0, &row1)) return UWVK_EINVAL;
+  if (row1 > row0 && !visual_rows_finite(vr, row0, row1)) return UWVK_ENAN;
   return UWVK_OK;
 }
 
@@ -800,8 +786,8 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
     if (chk != UWVK_OK) return chk;
   }
   if (first < 0 || count < 0 || first + count > log->epochs || log->adcp_cells > 8) return UWVK_EINVAL;
-  if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->stats) ||
-                track->capacity < track_records(first, count, track->every)))
+  if (track && !track_args_valid(track->every, track->capacity, track->mean || track->variance || track->stats, first,
+                                 count))
     return UWVK_EINVAL;
   if (fx && !fixes_valid(fx, first, count)) return UWVK_EINVAL;
   DelayedEvents events;
@@ -856,47 +842,19 @@ static uwvk_status run_log(uwvk_pose* h, const uwvk_pose_log* log, int64_t first
     vfl.resize((size_t)count);
     for (int64_t k = 0; k < count; k++)
       vfl[(size_t)k] = vis->visual_offset[first + k + 1] > vis->visual_offset[first + k] ? 1u : 0u;
-    const size_t nf = (size_t)vis->n_features;
-    const size_t w_pos = nf * 3, w_cov = vis->feature_cov ? 0 : nf * 4,
-                 w_mk = vis->marker_pose ? 0 : (size_t)vrows * 7, w_all = w_pos + w_cov + w_mk;
-    sg = stage_acquire(h->stages, w_all * 8);
+    const VisualRows vr(*vis);
+    sg = stage_acquire(h->stages, visual_rows_words(vr, vrows) * 8);
     if (!sg) return UWVK_ENOMEM;
-    double* hw = (double*)sg->host;
-    const double* dw = (const double*)sg->dev;
-    std::memcpy(hw, vis->feature_positions, w_pos * 8);
-    if (w_cov) std::memcpy(hw + w_pos, vis->shared_feature_cov, w_cov * 8);
-    if (w_mk) std::memcpy(hw + w_pos + w_cov, vis->shared_marker_pose + vrow0 * 7, w_mk * 8);
+    const size_t w_all = visual_rows_stage(vr, vrow0, vrows, (double*)sg->host, (const double*)sg->dev, &vra.va,
+                                           &vra.marker_rows);
     HIPCHK(hipMemcpyAsync(sg->dev, sg->host, w_all * 8, hipMemcpyHostToDevice, h->stream));
     sg->used = true;
-    vra.va.nf = vis->n_features;
-    vra.va.features = vis->features;
-    vra.va.fcov = vis->feature_cov ? vis->feature_cov : dw + w_pos;
-    vra.va.fcov_stride = vis->feature_cov ? (int64_t)nf * 4 : 0;
-    vra.va.fpos = dw;
-    vra.va.marker = vis->marker_pose;
-    vra.va.marker_stride = vis->marker_pose ? 7 : 0;
-    std::memcpy(vra.va.cov_marker, vis->cov_marker_pose, sizeof(vra.va.cov_marker));
-    std::memcpy(vra.va.cam, vis->camera, sizeof(vra.va.cam));
-    std::memcpy(vra.va.cam_in, vis->camera_in_imu, sizeof(vra.va.cam_in));
-    vra.marker_rows = w_mk ? dw + w_pos + w_cov : nullptr;
     vra.row_base = vrow0;
     vra.applied = vis->applied;
   }
   const EpochPlan plan = plan_run(hf, fx ? fx->host_flags + first : nullptr, dly ? events.flags.data() : nullptr,
                                   track ? track->every : 0, first, count, facts(h), vrows > 0 ? vfl.data() : nullptr);
-  // the slot is free again once the launches queued so far have passed: the
-  // event is recorded when this function returns, an early return after a
-  // failed launch included (a return before `used` is set leaves the slot free)
-  struct SlotDone {
-    StageSlot* sg;
-    hipStream_t st;
-    ~SlotDone() {
-      if (sg && sg->used && hipEventRecord(sg->done, st) != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        sg->used = false;
-      }
-    }
-  } slot_done{sg, h->stream};
+  const StageDone stage_done{sg, h->stream};  // when this function returns, early returns included
   const int s = h->store, nout = 3 * s + 2;
   int64_t r = 0;  // the next record of this call
   for (const Launch& l : plan.launches) {

@@ -16,7 +16,9 @@
 #include "uwvk_aug_dev.hpp"
 #include "../../include/uwvk.h"
 #include "uwvk_host.hpp"
+#include "uwvk_plan.hpp"
 #include "uwvk_stage.hpp"
+#include "uwvk_visual_rows.hpp"
 
 using namespace uwvk;
 using namespace uwvk::aug;
@@ -583,7 +585,9 @@ struct SmallHandle {
   SmallBufs bufs() const { return SmallBufs{batch, d_mu, d_sigma, d_status}; }
 };
 
-// StageSlot, stage_acquire, stage_release: the host arrays of one run call (uwvk_stage.hpp)
+// StageSlot, stage_acquire, StageDone, stage_release: the host arrays of one run call
+// (uwvk_stage.hpp); VisualRows: the checks and the staging of the visual rows
+// (uwvk_visual_rows.hpp)
 
 struct uwvk_bottom : SmallHandle {
   M9 Q{};
@@ -827,13 +831,13 @@ uwvk_status uwvk_bottom_run_log(uwvk_bottom* h, const uwvk_bottom_log* log, int6
   if (!h) return UWVK_EINVAL;
   const uwvk_status chk = uwvk_bottom_log_check(log, first, count);
   if (chk != UWVK_OK) return chk;
-  if (track && (track->every <= 0 || (!track->mean && !track->variance) ||
-                track->capacity < uwvk_pose_track_records(first, count, track->every)))
+  if (track && !track_args_valid(track->every, track->capacity, track->mean || track->variance, first, count))
     return UWVK_EINVAL;
   if (!h->has_state) return UWVK_ENOTINIT;
   if (count == 0) return UWVK_OK;
   StageSlot* sg = stage_acquire(h->stages, (size_t)count * sizeof(BottomEpoch));
   if (!sg) return UWVK_ENOMEM;
+  const StageDone stage_done{sg, h->stream};
   BottomEpoch* const table = (BottomEpoch*)sg->host;
   const uint32_t beam_bits = (1u << log->beams) - 1u;
   int32_t record = 0;
@@ -878,10 +882,6 @@ uwvk_status uwvk_bottom_run_log(uwvk_bottom* h, const uwvk_bottom_log* log, int6
     hipLaunchKernelGGL(k_bottom_run, dim3(grid_of(h->batch, BE::IPB)), dim3(BE::BLOCK), 0, h->stream, h->bufs(), a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) st = (uwvk_status)::uwvk::edevice_status(le, "k_bottom_run");
-  }
-  if (hipEventRecord(sg->done, h->stream) != hipSuccess) {  // cannot tell when the slot is free: wait now
-    (void)hipStreamSynchronize(h->stream);
-    sg->used = false;
   }
   return st;
 }
@@ -1056,34 +1056,16 @@ uwvk_status uwvk_ipose_log_check(const uwvk_ipose_log* log, int64_t first, int64
   } else if (!(log->dt > 0.0)) {
     return UWVK_EINVAL;
   }
-  int64_t row0 = 0, row1 = 0;
-  if (log->visual_offset) {
-    for (int64_t e = first; e <= first + count; e++) {
-      const int64_t o = log->visual_offset[e];
-      if (o < 0 || o > log->n_visual || (e > first && o < log->visual_offset[e - 1])) return UWVK_EINVAL;
-    }
-    row0 = log->visual_offset[first];
-    row1 = log->visual_offset[first + count];
-  }
-  if (row1 > row0) {
-    if (log->n_features < 1 || !log->features || !log->feature_positions) return UWVK_EINVAL;
-    if ((!log->feature_cov && !log->shared_feature_cov) || (!log->marker_pose && !log->shared_marker_pose))
-      return UWVK_EINVAL;
-  }
+  const VisualRows vr(*log);
+  int64_t row0, row1;
+  if (!visual_rows_valid(vr, first, count, &row0, &row1)) return UWVK_EINVAL;
   // the shared host values the range uses (checkMeasurment of the single calls)
   if (log->dt_epoch) {
     if (!finite_all(log->dt_epoch + first, (size_t)count)) return UWVK_ENAN;
   } else if (!std::isfinite(log->dt)) {
     return UWVK_ENAN;
   }
-  if (row1 > row0) {
-    const size_t nf = (size_t)log->n_features;
-    if (!log->feature_cov && !finite_all(log->shared_feature_cov, nf * 4)) return UWVK_ENAN;
-    if (!finite_all(log->feature_positions, nf * 3)) return UWVK_ENAN;
-    if (!log->marker_pose && !finite_all(log->shared_marker_pose + row0 * 7, (size_t)(row1 - row0) * 7)) return UWVK_ENAN;
-    if (!finite_all(log->cov_marker_pose, 36) || !finite_all(log->camera, 4) || !finite_all(log->camera_in_body, 7))
-      return UWVK_ENAN;
-  }
+  if (row1 > row0 && !visual_rows_finite(vr, row0, row1)) return UWVK_ENAN;
   return UWVK_OK;
 }
 
@@ -1093,25 +1075,22 @@ uwvk_status uwvk_ipose_run_log(uwvk_ipose* h, const uwvk_ipose_log* log, int64_t
   if (!h) return UWVK_EINVAL;
   const uwvk_status chk = uwvk_ipose_log_check(log, first, count);
   if (chk != UWVK_OK) return chk;
-  if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->corrected) ||
-                track->capacity < uwvk_pose_track_records(first, count, track->every)))
+  if (track && !track_args_valid(track->every, track->capacity, track->mean || track->variance || track->corrected,
+                                 first, count))
     return UWVK_EINVAL;
   if (!h->has_state) return UWVK_ENOTINIT;
   if (count == 0) return UWVK_OK;
+  const VisualRows vr(*log);
   const int64_t row0 = log->visual_offset ? log->visual_offset[first] : 0;
   const int64_t rows = log->visual_offset ? log->visual_offset[first + count] - row0 : 0;
-  const size_t nf = rows ? (size_t)log->n_features : 0;
-  // the staged words: feature positions, shared feature covariance, this call's
-  // shared marker poses, then the epoch table
-  const size_t w_pos = nf * 3, w_cov = (rows && !log->feature_cov) ? nf * 4 : 0,
-               w_mk = (rows && !log->marker_pose) ? (size_t)rows * 7 : 0, w_all = w_pos + w_cov + w_mk;
-  StageSlot* sg = stage_acquire(h->stages, w_all * 8 + (size_t)count * sizeof(IPoseEpoch));
+  // the staged words: the rows' shared visual inputs (visual_rows_stage), then the epoch table
+  StageSlot* sg = stage_acquire(h->stages, visual_rows_words(vr, rows) * 8 + (size_t)count * sizeof(IPoseEpoch));
   if (!sg) return UWVK_ENOMEM;
+  const StageDone stage_done{sg, h->stream};
   double* hw = (double*)sg->host;
   const double* dw = (const double*)sg->dev;
-  if (w_pos) std::memcpy(hw, log->feature_positions, w_pos * 8);
-  if (w_cov) std::memcpy(hw + w_pos, log->shared_feature_cov, w_cov * 8);
-  if (w_mk) std::memcpy(hw + w_pos + w_cov, log->shared_marker_pose + row0 * 7, w_mk * 8);
+  IPoseRunArgs a{};
+  const size_t w_all = visual_rows_stage(vr, row0, rows, hw, dw, &a.va, &a.marker_rows);
   IPoseEpoch* het = (IPoseEpoch*)(hw + w_all);
   int32_t record = 0;
   for (int64_t k = 0; k < count; k++) {
@@ -1125,9 +1104,7 @@ uwvk_status uwvk_ipose_run_log(uwvk_ipose* h, const uwvk_ipose_log* log, int64_t
   HIPCHK(hipMemcpyAsync(sg->dev, sg->host, w_all * 8 + (size_t)count * sizeof(IPoseEpoch), hipMemcpyHostToDevice,
                         h->stream));
   sg->used = true;
-  IPoseRunArgs a{};
   a.ref_io = h->d_aux;
-  a.marker_rows = w_mk ? dw + w_pos + w_cov : nullptr;
   a.row_base = row0;
   a.applied = applied;
   a.tr_mean = track ? track->mean : nullptr;
@@ -1135,18 +1112,6 @@ uwvk_status uwvk_ipose_run_log(uwvk_ipose* h, const uwvk_ipose_log* log, int64_t
   a.tr_corr = track ? track->corrected : nullptr;
   a.tau = h->tau;
   a.Q = h->Q;
-  if (rows) {
-    a.va.nf = log->n_features;
-    a.va.features = log->features;
-    a.va.fcov = log->feature_cov ? log->feature_cov : dw + w_pos;
-    a.va.fcov_stride = log->feature_cov ? (int64_t)nf * 4 : 0;
-    a.va.fpos = dw;
-    a.va.marker = log->marker_pose;
-    a.va.marker_stride = log->marker_pose ? 7 : 0;
-    std::memcpy(a.va.cov_marker, log->cov_marker_pose, sizeof(a.va.cov_marker));
-    std::memcpy(a.va.cam, log->camera, sizeof(a.va.cam));
-    std::memcpy(a.va.cam_in, log->camera_in_body, sizeof(a.va.cam_in));
-  }
   // one launch per chunk of epochs; the state's round trip through HBM is exact
   uwvk_status st = UWVK_OK;
   const dim3 grid(grid_of(h->batch, IAE<1>::IPB)), block(IAE<1>::BLOCK);
@@ -1158,10 +1123,6 @@ uwvk_status uwvk_ipose_run_log(uwvk_ipose* h, const uwvk_ipose_log* log, int64_t
     else hipLaunchKernelGGL(k_ipose_run<0>, grid, block, 0, h->stream, h->bufs(), a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) st = (uwvk_status)::uwvk::edevice_status(le, "k_ipose_run");
-  }
-  if (hipEventRecord(sg->done, h->stream) != hipSuccess) {  // cannot tell when the slot is free: wait now
-    (void)hipStreamSynchronize(h->stream);
-    sg->used = false;
   }
   return st;
 }

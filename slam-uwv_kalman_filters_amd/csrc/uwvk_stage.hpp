@@ -4,7 +4,8 @@
 // rows of the call): written into pinned host memory before the call returns,
 // copied to the device on the handle's stream.  A slot is free again once the
 // event behind its last launch has passed, so a later call never overwrites
-// what a queued launch still reads.
+// what a queued launch still reads (StageDone records that event for every
+// caller).  What the visual rows put into a slot: uwvk_visual_rows.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,5 +64,21 @@ inline StageSlot* stage_acquire(std::vector<StageSlot>& stages, size_t bytes) {
   }
   return s;
 }
+
+// Marks a slot whose copy has been queued (`used` set) as free again once the
+// launches queued so far have passed: the event is recorded when the scope
+// ends, an early return after a failed copy or launch included (a return
+// before `used` is set leaves the slot free).  If the event cannot be
+// recorded there is no telling when the slot is free: wait now.
+struct StageDone {
+  StageSlot* sg;  // nullable
+  hipStream_t st;
+  ~StageDone() {
+    if (sg && sg->used && hipEventRecord(sg->done, st) != hipSuccess) {
+      (void)hipStreamSynchronize(st);
+      sg->used = false;
+    }
+  }
+};
 
 }  // namespace uwvk

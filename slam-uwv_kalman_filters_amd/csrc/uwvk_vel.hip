@@ -3,6 +3,11 @@
 // z position) with 9 sigma points, so Sigma, the sigma points and the RK4
 // integration of the [EXT] uwv_dynamic_model ModelSimulation all live in
 // VGPRs; the kernel is bound by the fp64 model evaluation (9 x RK4 per predict).
+// The multi-epoch run (uwvk_vel_run_log, uwvk_vel_run_log_track) has one host
+// launcher, vel_run, and for the row layout (a DPP row per filter) one epoch
+// body, vel_epoch_g_body, instantiated plain and screened behind the
+// k_vel_epoch_g* kernels; the lane-per-filter kernels k_vel_epoch and
+// k_vel_epoch_track are written out separately (see there).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +17,7 @@
 
 #include "uwvk_dev.hpp"
 #include "uwvk_host.hpp"
+#include "uwvk_plan.hpp"
 
 using namespace uwvk;
 
@@ -499,6 +505,12 @@ __global__ __launch_bounds__(64) void k_vel_epoch(VelBufs b, VelShared P0, VelEp
 }
 
 // ---- uwvk_vel_run_log_track: the same epochs, screened, with records ---------
+// The row layout has one body for both (vel_epoch_g_body<VG, TRACK> below).
+// The lane-per-filter pair stays two functions: as two instantiations of one
+// force-inlined body the screened kernel's register allocation came out 1.0%
+// slower at batch 65,536 (26.07 against 25.80 ms per 1,000 epochs, round-to-
+// round spread 0.12 ms; arguments by reference: 10%), the plain one 3% faster
+// (profiles/EXPERIMENTS.md, "run_log: one body ...").
 // What the screened kernels take beside VelEpochArgs.  The record epochs of a
 // launch are next, next + every, ...: the host places the first one, so the
 // kernels compare and add (no 64-bit modulo per epoch).
@@ -811,25 +823,46 @@ UWVK_DEV bool vg_update(double mu[4], double S[16], const double z[M], const dou
 // C2's batch 4,096, which needs <= 256 VGPR + AGPR: amdgpu_waves_per_eu(2)).
 // It prices the latency hiding a 32-lane split would get before any of the
 // split's own savings.
-
+//
+// vel_epoch_g_body is the epoch loop of the row layout for both kernels:
+// k_vel_epoch_g<VG> is TRACK = false (the plain run: no load of the stored
+// w / tau, no finite tests, no counters or records, the status only ever gets
+// UWVK_ST_NOTPD), k_vel_epoch_g_track<VG> is TRACK = true.
 // (r04) loop-invariant scalar data (Q0, the DVL covariance) loaded where it is
 // used: hoisted out of the epoch loop it held 50 SGPRs, which the register
-// allocator spilled to VGPR lanes and restored with v_readlane every epoch
-
-template <int VG>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG / 16))) void k_vel_epoch_g(VelBufs b, VelShared P0, VelEpochArgs ea) {
+// allocator spilled to VGPR lanes and restored with v_readlane every epoch.
+// TRACK adds screening and records (uwvk_vel_run_log_track).  One
+// filter per DPP row, so a skip is uniform within a row and not within the
+// wave: the skipped steps sit in row-uniform branches, and every cross-lane
+// operation inside them (row_sum16, row_bcast_c, the DPP moves) reads lanes of
+// its own row, which took the same branch.  The samples are the same address
+// in every lane of a row, so the finite tests are row-uniform by construction.
+// The fetch one epoch ahead stays; the fetched inputs are tested when they
+// become current.  The side lane (9) holds m and a replica of mu / Sigma and
+// writes the records; dead rows and the VG = 32 shadow row store nothing.
+template <int VG, bool TRACK>
+UWVK_DEV void vel_epoch_g_body(VelBufs b, VelShared P0, VelEpochArgs ea, VelTrackArgs ta) {
   VEL_PARAMS(b, P0);
   const int g = (int)threadIdx.x & 15;
   const int64_t B = b.batch, inst = (int64_t)blockIdx.x * (64 / VG) + (int)threadIdx.x / VG;
   const bool live = inst < B;
   const int64_t i = live ? inst : B - 1;  // dead groups compute on a copy and store nothing
   const bool pt = g < 9, side = g == 9;
+  const bool writer = side && live && !(VG == 32 && (threadIdx.x & 16));
   double mu[4], S[16], m[13], w[3], tau[6];
   v_load(b, i, mu, S);
 #pragma unroll
   for (int k = 0; k < 13; k++) m[k] = b.model[i * 13 + k];
+  if constexpr (TRACK) {  // what an instance without a finite epoch writes back
+#pragma unroll
+    for (int k = 0; k < 3; k++) w[k] = b.gyro[i * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) tau[k] = b.efforts[i * 6 + k];
+  }
   double q[4] = {m[3], m[4], m[5], m[6]};
   bool ok = true;
+  uint32_t st = 0, n_dvl = 0, n_p = 0;
+  int64_t rec_e = ta.next, rec = ta.record;
   // (r04) the next epoch's gyro / efforts / flag word issued one epoch ahead:
   // at one wave per SIMD the loads' latency was exposed at the top of every epoch
   double w_n[3] = {0, 0, 0}, tau_n[6] = {0, 0, 0, 0, 0, 0};
@@ -844,120 +877,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG 
   if (ea.count > 0) fetch(ea.first);
   for (int64_t e = ea.first; e < ea.first + ea.count; e++) {
     const uint32_t fl = __builtin_amdgcn_readfirstlane(fl_n);
-#pragma unroll
-    for (int k = 0; k < 3; k++) { w[k] = w_n[k]; m[10 + k] = w[k]; }
-#pragma unroll
-    for (int k = 0; k < 6; k++) tau[k] = tau_n[k];
-    if (e + 1 < ea.first + ea.count) fetch(e + 1);
-    // predict (VelocityUKF.cpp:115-128): point lanes integrate their sigma
-    // point, lane 9 the side model, in one RK4 pass
-    double L[16], x[4];
-    ok = v_chol(S, L) && ok;
-    vg_point(mu, L, g, x);
-    double s13[13], n13[13];
-#pragma unroll
-    for (int k = 0; k < 13; k++) s13[k] = m[k];
-    if (!side) {
-      s13[0] = s13[1] = s13[2] = 0.0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) s13[3 + k] = q[k];
-#pragma unroll
-      for (int k = 0; k < 3; k++) s13[7 + k] = x[k];
-    }
-    v_rk4(P, tau, ea.dt, s13, n13);
-    {  // processMotionModel tail (VelocityUKF.cpp:22-32)
-      double t[3], r[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) t[k] = x[k] + (n13[7 + k] - x[k]);
-      qrot(q, t, r);
-      x[3] = x[3] + ea.dt * r[2];
-      x[0] = t[0]; x[1] = t[1]; x[2] = t[2];
-    }
-    vg_mean<4>(x, pt, mu);
-    vg_cov(x, mu, pt, S);
-    {  // Q0 by scalar loads here, not hoisted out of the loop into 32 SGPRs held across it
-      const auto& PQ = vlaunder(P);
-#pragma unroll
-      for (int k = 0; k < 16; k++) S[k] += ea.dt * PQ.Q0[k];
-    }
-    if (side) {
-#pragma unroll
-      for (int k = 0; k < 13; k++) m[k] = n13[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) q[k] = row_bcast_c<9>(side ? m[3 + k] : 0.0);
-    if (fl & UWVK_EV_DVL) {
-      const double* z = ea.dvl + ((int64_t)ea.dvl_index[e] * B + i) * 3;
-      const double zz[3] = {z[0], z[1], z[2]};
-      const double* Rd = ea.dvl_cov;
-      asm volatile("" : "+s"(Rd));  // R loaded in the branch, not held in SGPRs across the loop
-      ok = vg_update<3, 0>(mu, S, zz, Rd, g) && ok;
-    }
-    if (fl & UWVK_EV_PRESSURE) {
-      const double zz[1] = {ea.pressure[(int64_t)ea.p_index[e] * B + i]};
-      const double R[1] = {ea.p_cov};
-      ok = vg_update<1, 3>(mu, S, zz, R, g) && ok;
-    }
-  }
-  if (!live) return;
-  if (VG == 32 && (threadIdx.x & 16)) return;  // the shadow row
-  if (side) {
-    if (ea.count > 0) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) b.gyro[i * 3 + k] = w[k];
-#pragma unroll
-      for (int k = 0; k < 6; k++) b.efforts[i * 6 + k] = tau[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 13; k++) b.model[i * 13 + k] = m[k];
-    if (!ok) b.status[i] |= UWVK_ST_NOTPD;
-    v_store(b, i, mu, S);
-  }
-}
-
-// k_vel_epoch_g with screening and records (uwvk_vel_run_log_track).  One
-// filter per DPP row, so a skip is uniform within a row and not within the
-// wave: the skipped steps sit in row-uniform branches, and every cross-lane
-// operation inside them (row_sum16, row_bcast_c, the DPP moves) reads lanes of
-// its own row, which took the same branch.  The samples are the same address
-// in every lane of a row, so the finite tests are row-uniform by construction.
-// The fetch one epoch ahead stays; the fetched inputs are tested when they
-// become current.  The side lane (9) holds m and a replica of mu / Sigma and
-// writes the records; dead rows and the VG = 32 shadow row store nothing.
-template <int VG>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG / 16))) void k_vel_epoch_g_track(VelBufs b, VelShared P0, VelEpochArgs ea, VelTrackArgs ta) {
-  VEL_PARAMS(b, P0);
-  const int g = (int)threadIdx.x & 15;
-  const int64_t B = b.batch, inst = (int64_t)blockIdx.x * (64 / VG) + (int)threadIdx.x / VG;
-  const bool live = inst < B;
-  const int64_t i = live ? inst : B - 1;  // dead groups compute on a copy and store nothing
-  const bool pt = g < 9, side = g == 9;
-  const bool writer = side && live && !(VG == 32 && (threadIdx.x & 16));
-  double mu[4], S[16], m[13], w[3], tau[6];
-  v_load(b, i, mu, S);
-#pragma unroll
-  for (int k = 0; k < 13; k++) m[k] = b.model[i * 13 + k];
-#pragma unroll
-  for (int k = 0; k < 3; k++) w[k] = b.gyro[i * 3 + k];  // what an instance without a finite epoch writes back
-#pragma unroll
-  for (int k = 0; k < 6; k++) tau[k] = b.efforts[i * 6 + k];
-  double q[4] = {m[3], m[4], m[5], m[6]};
-  bool ok = true;
-  uint32_t st = 0, n_dvl = 0, n_p = 0;
-  int64_t rec_e = ta.next, rec = ta.record;
-  double w_n[3] = {0, 0, 0}, tau_n[6] = {0, 0, 0, 0, 0, 0};
-  uint32_t fl_n = 0;
-  auto fetch = [&](int64_t e) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) w_n[k] = ea.gyro[(e * B + i) * 3 + k];
-#pragma unroll
-    for (int k = 0; k < 6; k++) tau_n[k] = ea.efforts[(e * B + i) * 6 + k];
-    fl_n = ea.flags[e + (g >> 4)];  // a lane-dependent (zero) offset: a VGPR until used
-  };
-  if (ea.count > 0) fetch(ea.first);
-  for (int64_t e = ea.first; e < ea.first + ea.count; e++) {
-    const uint32_t fl = __builtin_amdgcn_readfirstlane(fl_n);
-    const bool fin = v_finite(w_n) && v_finite(tau_n);
+    const bool fin = !TRACK || (v_finite(w_n) && v_finite(tau_n));
     if (fin) {
 #pragma unroll
       for (int k = 0; k < 3; k++) { w[k] = w_n[k]; m[10 + k] = w[k]; }
@@ -1009,7 +929,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG 
     if (fl & UWVK_EV_DVL) {
       const double* z = ea.dvl + ((int64_t)ea.dvl_index[e] * B + i) * 3;
       const double zz[3] = {z[0], z[1], z[2]};
-      if (v_finite(zz)) {
+      if (!TRACK || v_finite(zz)) {
         const double* Rd = ea.dvl_cov;
         asm volatile("" : "+s"(Rd));  // R loaded in the branch, not held in SGPRs across the loop
         ok = vg_update<3, 0>(mu, S, zz, Rd, g) && ok;
@@ -1021,14 +941,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG 
     if (fl & UWVK_EV_PRESSURE) {
       const double zz[1] = {ea.pressure[(int64_t)ea.p_index[e] * B + i]};
       const double R[1] = {ea.p_cov};
-      if (v_finite(zz)) {
+      if (!TRACK || v_finite(zz)) {
         ok = vg_update<1, 3>(mu, S, zz, R, g) && ok;
         n_p++;
       } else {
         st |= UWVK_ST_NAN;
       }
     }
-    if (e == rec_e) {
+    if (TRACK && e == rec_e) {
       if (writer) v_record(ta, rec * B + i, mu, S, m);
       rec++;
       rec_e += ta.every;
@@ -1045,11 +965,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG 
   for (int k = 0; k < 13; k++) b.model[i * 13 + k] = m[k];
   if (!ok) st |= UWVK_ST_NOTPD;
   if (st) b.status[i] |= st;
-  if (ta.applied) {
+  if (TRACK && ta.applied) {
     ta.applied[i * 2] += n_dvl;
     ta.applied[i * 2 + 1] += n_p;
   }
   v_store(b, i, mu, S);
+}
+
+template <int VG>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG / 16))) void k_vel_epoch_g(VelBufs b, VelShared P0, VelEpochArgs ea) {
+  vel_epoch_g_body<VG, false>(b, P0, ea, VelTrackArgs{});
+}
+template <int VG>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VG / 16, VG / 16))) void k_vel_epoch_g_track(VelBufs b, VelShared P0, VelEpochArgs ea, VelTrackArgs ta) {
+  vel_epoch_g_body<VG, true>(b, P0, ea, ta);
 }
 
 __global__ void k_vel_setup(VelBufs b) {  // setupMotionModel pose (VelocityUKF.cpp:65-74)
@@ -1337,33 +1266,50 @@ uwvk_status uwvk_vel_get_status(uwvk_vel* h, uint32_t* status, int clear) {
   return UWVK_OK;
 }
 
-uwvk_status uwvk_vel_run_log(uwvk_vel* h, const uwvk_vel_log* log, int64_t first, int64_t count) {
-  UWVK_DEVICE_GUARD(h);
-  if (!h || !log || first < 0 || count < 0 || first + count > log->epochs) return UWVK_EINVAL;
-  if (!h->has_model) return UWVK_ENOMODEL;
+// The launches of both run_log entry points, after their argument checks: one
+// launch per chunk of epochs (the state stays in registers across the chunk; a
+// record does not end a launch), in the handle's layout.  screened == NULL
+// runs the plain kernels; otherwise the screened ones with *screened, whose
+// record position is placed per chunk when it has a track (every > 0).
+static uwvk_status vel_run(uwvk_vel* h, const uwvk_vel_log* log, int64_t first, int64_t count,
+                           const VelTrackArgs* screened) {
   VelEpochArgs ea{};
   ea.flags = log->flags; ea.gyro = log->gyro; ea.efforts = log->efforts;
   ea.dvl_index = log->dvl_index; ea.dvl = log->dvl;
   std::memcpy(ea.dvl_cov, log->dvl_cov, sizeof(ea.dvl_cov));
   ea.p_index = log->pressure_index; ea.pressure = log->pressure; ea.p_cov = log->pressure_cov;
   ea.dt = log->dt;
-  // one launch per chunk of epochs (state stays in registers across the chunk)
+  VelTrackArgs ta = screened ? *screened : VelTrackArgs{};
   const bool groups = h->groups > 0 || (h->groups < 0 && h->batch <= kVelGroupsMaxBatch);
+  const int vg = !groups ? 0 : h->groups == 2 ? 32 : 16;  // lanes per filter (0: one lane)
+  const dim3 grid(vg ? (unsigned)((h->batch + 64 / vg - 1) / (64 / vg)) : vgrid(h->batch)), block(64);
   constexpr int64_t kChunk = 4096;
   for (int64_t e = first; e < first + count; e += kChunk) {
     ea.first = e;
     ea.count = std::min<int64_t>(kChunk, first + count - e);
-    if (groups && h->groups == 2)
-      hipLaunchKernelGGL(k_vel_epoch_g<32>, dim3((unsigned)((h->batch + 1) / 2)), dim3(64), 0, h->stream, vbufs(h),
-                         h->P, ea);
-    else if (groups)
-      hipLaunchKernelGGL(k_vel_epoch_g<16>, dim3((unsigned)((h->batch + 3) / 4)), dim3(64), 0, h->stream, vbufs(h),
-                         h->P, ea);
-    else
-      hipLaunchKernelGGL(k_vel_epoch, dim3(vgrid(h->batch)), dim3(64), 0, h->stream, vbufs(h), h->P, ea);
+    if (ta.every > 0) {
+      ta.next = e + (ta.every - 1 - e % ta.every);
+      ta.record = track_records(first, e - first, ta.every);
+    }
+    if (screened) {
+      if (vg == 32) hipLaunchKernelGGL(k_vel_epoch_g_track<32>, grid, block, 0, h->stream, vbufs(h), h->P, ea, ta);
+      else if (vg == 16) hipLaunchKernelGGL(k_vel_epoch_g_track<16>, grid, block, 0, h->stream, vbufs(h), h->P, ea, ta);
+      else hipLaunchKernelGGL(k_vel_epoch_track, grid, block, 0, h->stream, vbufs(h), h->P, ea, ta);
+    } else {
+      if (vg == 32) hipLaunchKernelGGL(k_vel_epoch_g<32>, grid, block, 0, h->stream, vbufs(h), h->P, ea);
+      else if (vg == 16) hipLaunchKernelGGL(k_vel_epoch_g<16>, grid, block, 0, h->stream, vbufs(h), h->P, ea);
+      else hipLaunchKernelGGL(k_vel_epoch, grid, block, 0, h->stream, vbufs(h), h->P, ea);
+    }
     HIPCHK(hipGetLastError());
   }
   return UWVK_OK;
+}
+
+uwvk_status uwvk_vel_run_log(uwvk_vel* h, const uwvk_vel_log* log, int64_t first, int64_t count) {
+  UWVK_DEVICE_GUARD(h);
+  if (!h || !log || first < 0 || count < 0 || first + count > log->epochs) return UWVK_EINVAL;
+  if (!h->has_model) return UWVK_ENOMODEL;
+  return vel_run(h, log, first, count, nullptr);
 }
 
 // host only (no HIP call): what uwvk_vel_run_log_track checks before it queues anything
@@ -1398,16 +1344,10 @@ uwvk_status uwvk_vel_run_log_track(uwvk_vel* h, const uwvk_vel_log* log, const u
   if (!h) return UWVK_EINVAL;
   const uwvk_status chk = uwvk_vel_log_check(log, host, first, count);
   if (chk != UWVK_OK) return chk;
-  if (track && (track->every <= 0 || (!track->mean && !track->variance && !track->model) ||
-                track->capacity < uwvk_pose_track_records(first, count, track->every)))
+  if (track && !track_args_valid(track->every, track->capacity, track->mean || track->variance || track->model, first,
+                                 count))
     return UWVK_EINVAL;
   if (!h->has_model) return UWVK_ENOMODEL;
-  VelEpochArgs ea{};
-  ea.flags = log->flags; ea.gyro = log->gyro; ea.efforts = log->efforts;
-  ea.dvl_index = log->dvl_index; ea.dvl = log->dvl;
-  std::memcpy(ea.dvl_cov, log->dvl_cov, sizeof(ea.dvl_cov));
-  ea.p_index = log->pressure_index; ea.pressure = log->pressure; ea.p_cov = log->pressure_cov;
-  ea.dt = log->dt;
   VelTrackArgs ta{};
   ta.applied = applied;
   ta.next = -1;
@@ -1415,28 +1355,7 @@ uwvk_status uwvk_vel_run_log_track(uwvk_vel* h, const uwvk_vel_log* log, const u
     ta.mean = track->mean; ta.variance = track->variance; ta.model = track->model;
     ta.every = track->every;
   }
-  // one launch per chunk of epochs, the layout choice of uwvk_vel_run_log; a
-  // record does not end a launch
-  const bool groups = h->groups > 0 || (h->groups < 0 && h->batch <= kVelGroupsMaxBatch);
-  constexpr int64_t kChunk = 4096;
-  for (int64_t e = first; e < first + count; e += kChunk) {
-    ea.first = e;
-    ea.count = std::min<int64_t>(kChunk, first + count - e);
-    if (track) {
-      ta.next = e + (track->every - 1 - e % track->every);
-      ta.record = uwvk_pose_track_records(first, e - first, track->every);
-    }
-    if (groups && h->groups == 2)
-      hipLaunchKernelGGL(k_vel_epoch_g_track<32>, dim3((unsigned)((h->batch + 1) / 2)), dim3(64), 0, h->stream,
-                         vbufs(h), h->P, ea, ta);
-    else if (groups)
-      hipLaunchKernelGGL(k_vel_epoch_g_track<16>, dim3((unsigned)((h->batch + 3) / 4)), dim3(64), 0, h->stream,
-                         vbufs(h), h->P, ea, ta);
-    else
-      hipLaunchKernelGGL(k_vel_epoch_track, dim3(vgrid(h->batch)), dim3(64), 0, h->stream, vbufs(h), h->P, ea, ta);
-    HIPCHK(hipGetLastError());
-  }
-  return UWVK_OK;
+  return vel_run(h, log, first, count, &ta);
 }
 
 }  // extern "C"

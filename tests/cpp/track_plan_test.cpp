@@ -107,6 +107,19 @@ int main() {
     CHECK(!segs.empty() && segs.front().first == first && segs.back().first + segs.back().count == first + count);
     CHECK((int64_t)records(first, count, every).size() == track_records(first, count, every));
   }
+  // track_args_valid, the track argument check of every run_log entry point: a
+  // stride <= 0, no output array, and the capacity one below / exactly at the
+  // records of a range that does not start at 0 ([13, 53) with every 7: after epochs 13, 20, .. 48)
+  {
+    const int64_t first = 13, count = 40, every = 7, need = track_records(first, count, every);
+    CHECK(need == 6);
+    CHECK(!track_args_valid(0, need, true, first, count));
+    CHECK(!track_args_valid(-every, need, true, first, count));
+    CHECK(!track_args_valid(every, need, false, first, count));
+    CHECK(!track_args_valid(every, need - 1, true, first, count));
+    CHECK(track_args_valid(every, need, true, first, count));
+    CHECK(track_args_valid(every, 0, true, first, 0));  // an empty range needs no room
+  }
   std::printf("track plan: %s\n", g_fail ? "FAILED" : "ok");
   return g_fail ? 1 : 0;
 }
