@@ -39,6 +39,7 @@
 
 #include "uwvk_pose_dev.hpp"
 #include "uwvk_tiles.hpp"
+#include "uwvk_bcast.hpp"
 
 // r05: the compile-time A/B knobs of rounds 1-4 (PSP_*: lane-limited wave
 // sums, LDS broadcasts, the three rank-M MFMA forms, lane masks, SGPR series
@@ -242,6 +243,66 @@ UWVK_DEV double hbc(double v) {
   lo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xa, 0xf, false);
   hi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xa, 0xf, false);
   return __hiloint2double(hi, lo);
+}
+// (r10) A broadcast fused into the fp64 FMA that consumes it: v_fmac_f64 is
+// VOP2 and takes a DPP row_newbcast:N source, every lane of a 16-lane row its
+// row's lane N.  rep16 first puts the half's lower row into both of its rows
+// (lo) and the upper row likewise (hi), one v_permlane16_swap_b32 per dword
+// (uwvk_bcast.hpp); local lane s of the half is then row_newbcast:(s & 15) of
+// lo (s < 16) or hi.  No LDS write, ordering point or read, and no
+// instruction for the broadcast itself.
+// The half must be fully active at every use: row_newbcast reads the source
+// lane's register, and a source lane outside EXEC suppresses the write.  The
+// users (the predict's Delta loop, the update's P / Dz loop) are straight-line
+// code with lane conditions as selects, not branches (no s_cbranch or EXEC
+// write between their first and last v_fmac_f64_dpp in the ISA); a wave whose
+// other half skips an update runs them with that half off, which leaves this
+// half whole.  The partial Cholesky's column pairs stay in LDS: read this way
+// they cost 18 rep16 per epoch and measured slower on top of the Delta loop
+// (profiles/EXPERIMENTS.md r10).
+// The compiler does not look inside the assembly for the 2 wait states
+// between a VALU write of a DPP source and the DPP read: bc_ready puts one
+// s_nop 1 between the replicated copies and everything that reads them, once
+// per loop and not per FMA (tools/isa_bcast_hazard.py checks the ISA; the
+// accumulator and the second factor are ordinary interlocked VALU operands,
+// tools/probe_dpp64.hip).
+UWVK_DEV void rep16(double v, double& lo, double& hi) {
+  const unsigned vl = (unsigned)__double2loint(v), vh = (unsigned)__double2hiint(v);
+  const auto l = __builtin_amdgcn_permlane16_swap(vl, vl, false, false);
+  const auto h = __builtin_amdgcn_permlane16_swap(vh, vh, false, false);
+  lo = __hiloint2double((int)h[0], (int)l[0]);
+  hi = __hiloint2double((int)h[1], (int)l[1]);
+}
+UWVK_DEV void bc_ready(double& r0, double& r1, double& r2, double& r3) {
+  asm("s_nop 1" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
+}
+UWVK_DEV void bc_ready(double& r0, double& r1, double& r2, double& r3, double& r4) {
+  asm("s_nop 1" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4));
+}
+UWVK_DEV void bc_ready(double& r0, double& r1, double& r2, double& r3, double& r4, double& r5) {
+  asm("s_nop 1" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5));
+}
+// acc + bcast_N(rep) * own and acc - bcast_N(rep) * own, one rounding
+template <int N>
+UWVK_DEV double fmac_bc(double acc, double rep, double own) {
+  static_assert(N >= 0 && N < bcast::kRow, "row_newbcast lane");
+  asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(rep), "v"(own), "n"(N));
+  return acc;
+}
+template <int N>
+UWVK_DEV double fnmac_bc(double acc, double rep, double own) {
+  static_assert(N >= 0 && N < bcast::kRow, "row_newbcast lane");
+  asm("v_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(rep), "v"(own), "n"(N));
+  return acc;
+}
+// the same for local lane S < 32 of the half, from rep16's two copies
+template <int S>
+UWVK_DEV double fmac_bcs(double acc, double lo, double hi, double own) {
+  return fmac_bc<bcast::n_of(S)>(acc, bcast::copy_of(S) ? hi : lo, own);
+}
+template <int S>
+UWVK_DEV double fnmac_bcs(double acc, double lo, double hi, double own) {
+  return fnmac_bc<bcast::n_of(S)>(acc, bcast::copy_of(S) ? hi : lo, own);
 }
 #endif
 UWVK_DEV double hread(double v, int j) {
@@ -625,6 +686,34 @@ UWVK_DEV void pchol_step2_lds(double (&a)[K], const double (&f)[K], int r, bool&
     pchol_step2_lds<K, J + 2>(a, f, r, ok, col2, pnext);
   }
 }
+// (r10) Y += a[j] Delta_j with Delta_j[i] in lane 2j of the half (dlo / dhi:
+// rep16's copies of the three components), j = J .. K - 1 in order
+template <int K, int J>
+UWVK_DEV void delta_bc(double (&Y)[3], const double (&a)[K], const double (&dlo)[3], const double (&dhi)[3]) {
+  if constexpr (J < K) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) Y[i] = fmac_bcs<2 * J>(Y[i], dlo[i], dhi[i], a[J]);
+    delta_bc<K, J + 1>(Y, a, dlo, dhi);
+  }
+}
+// (r10) g[i] -= a[j] P[i][j] (P[i][j] in lane i K + j: plo / phi) and
+// c[i] += a[j] Dz_j[i] (Dz_j in lane 2j < 16: zlo), j = J .. K - 1 in order.
+// The first subtraction carries the pending scale of G: g[i] = fma(Gr[i], ds,
+// -(a[0] P[i][0])) -- the product rounded on its own (an FMA onto -0.0), the
+// scaling fused -- which is how the staged form's j = 0 step was compiled
+// (v_mul_f64, then v_fma_f64 with the scale), like the Cholesky's first pair.
+template <int M, int K, int J, int I = 0>
+UWVK_DEV void pdz_bc(double (&g)[M], double (&c)[M], const double (&a)[K], double plo, double phi,
+                     const double (&zlo)[M], const double (&Gr)[M], double ds) {
+#pragma clang fp contract(off)
+  if constexpr (J < K) {
+    if constexpr (J == 0) g[I] = fma(Gr[I], ds, -fmac_bcs<I * K>(-0.0, plo, phi, a[0]));
+    else g[I] = fnmac_bcs<I * K + J>(g[I], plo, phi, a[J]);
+    c[I] = fmac_bc<2 * J>(c[I], zlo[I], a[J]);
+    if constexpr (I + 1 < M) pdz_bc<M, K, J, I + 1>(g, c, a, plo, phi, zlo, Gr, ds);
+    else pdz_bc<M, K, J + 1, 0>(g, c, a, plo, phi, zlo, Gr, ds);
+  }
+}
 #endif
 
 // staged rows of L_a start here inside sm.stg; the Cholesky column buffer is
@@ -942,12 +1031,25 @@ UWVK_DEV bool psp_predict(PspSmem<DOF>& sm, const PoseShared& sh, const ProcCtx&
   chain_prio_hi();  // the broadcast loop over Delta_j is a chain too (see chain_prio_hi)
   {
     double Y[3] = {0.0, 0.0, 0.0};
-    // Delta_j staged in stg (free after the ori x ori sums) by lane 2j and read
+    // One instance per wave: Delta_j staged in stg (free after the ori x ori
+    // sums) by lane 2j and read
     // back by every lane as a broadcast, one j at a time (a compiler memory
     // barrier per j keeps at most two j's loads in flight: hoisted all at once
     // they took 90 VGPRs); 45 LDS reads instead of 90 v_readlane
     // (PSP_LDS_ALIGN: 4 slots per j from slot 1, so each j's first pair is one
     // aligned ds_read_b128)
+#if PSP_PAIR
+    // (r10) pair: Delta_j read from lane 2j's registers inside the FMA (rep16,
+    // fmac_bc; the sources span both DPP rows of the half) instead of the 15
+    // staged rows, their two ordering points and 30 LDS reads: the same 45
+    // FMAs in the same order (20 epochs -2.2%, 200 epochs -2.7%, profiles/r10/)
+    static_assert(2 * K <= 32, "Delta lanes within the half");
+    double dlo[3], dhi[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) rep16(dd[i], dlo[i], dhi[i]);
+    bc_ready(dlo[0], dlo[1], dlo[2], dhi[0], dhi[1], dhi[2]);
+    delta_bc<K, 0>(Y, a, dlo, dhi);
+#else
     constexpr int DS = 4, D0 = 1;
     static_assert(D0 + DS * K <= PG<DOF>::STG, "Delta (PG::STG)");
     if (LANE_IF(l, (l & 1) == 0 && l < 2 * K)) {
@@ -971,6 +1073,7 @@ UWVK_DEV bool psp_predict(PspSmem<DOF>& sm, const PoseShared& sh, const ProcCtx&
       asm volatile("" : "+v"(Y[0]), "+v"(Y[1]), "+v"(Y[2])::"memory");
     }
     wsync();  // stg is rewritten by the next phase's users
+#endif
     chain_prio_lo();
     const int cp = proc_couple(l);
     const int src = cp >= 0 ? cp : l;
@@ -1823,8 +1926,11 @@ UWVK_DEV bool psp_update(PspSmem<DOF>& sm, const double (&z)[HM::M], const doubl
 #pragma unroll
     for (int i = 0; i < M; i++) Gr[i] = hfma(Hs[i][t], s, Gr[i]);
   }
+  // Sigma[r][c] = d_r d_c Sigma~[r][c] (pair, K > 0: the scale goes into pdz_bc's first step)
+  if constexpr (!(PSP_PAIR && K > 0)) {
 #pragma unroll
-  for (int i = 0; i < M; i++) Gr[i] = Gr[i] * ds;  // Sigma[r][c] = d_r d_c Sigma~[r][c]
+    for (int i = 0; i < M; i++) Gr[i] = Gr[i] * ds;
+  }
   PSP_PHASE(32);
   // Glin_r = G_r - sum_j L[r][j] P[:, j]: row r of (Sigma - L_a L_a^T) H^T;
   // C_r = Glin_r + 1/2 sum_j L[r][j] Dz_j; S += H Glin + R  (H Glin = H Sigma H^T - P P^T)
@@ -1835,6 +1941,25 @@ UWVK_DEV bool psp_update(PspSmem<DOF>& sm, const double (&z)[HM::M], const doubl
     // (PSP_DELTA_LDS): LDS reads instead of 4 M K v_readlane
     // (PSP_LDS_ALIGN: M = 3 rows padded to 4 from slot 1, so each j's first
     // pair is one aligned ds_read_b128)
+#if PSP_PAIR
+    // (r10) pair: P[i][j] and Dz_j read from their lanes' registers inside the
+    // FMAs (rep16, fmac_bc); lanes >= 16 (M K = 18) come from the upper row's
+    // copy (on top of the Delta loop: 20 epochs -1.5%, 200 epochs -1.7%)
+    static_assert(M * K <= 32 && 2 * K <= 16, "P lanes within the half, Dz lanes within its lower row");
+    double g[M], c[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) g[i] = c[i] = 0.0;  // (g is set by the first step)
+    {
+      double plo, phi, zlo[M], zu;
+      rep16(Pl, plo, phi);
+#pragma unroll
+      for (int i = 0; i < M; i++) rep16(zd[i], zlo[i], zu);
+      if constexpr (M == 3) bc_ready(plo, phi, zlo[0], zlo[1], zlo[2]);
+      else if constexpr (M == 2) bc_ready(plo, phi, zlo[0], zlo[1]);
+      else static_assert(M == 2 || M == 3, "pair updates: M = 2 (ADCP) or 3");
+      pdz_bc<M, K, 0>(g, c, a, plo, phi, zlo, Gr, ds);
+    }
+#else
     constexpr int PS = M == 3 ? 4 : M, P0 = M >= 2 ? 1 : 0;
     static_assert(P0 + 2 * PS * K <= PG<DOF>::STG, "P and Dz (PG::STG)");
     if (LANE_IF(l, l < M * K)) sm.stg[P0 + (l % K) * PS + l / K] = Pl;  // j-major: P[i][j] at j PS + i
@@ -1865,6 +1990,7 @@ UWVK_DEV bool psp_update(PspSmem<DOF>& sm, const double (&z)[HM::M], const doubl
       }
     }
     wsync();  // stg is rewritten by the rank-M staging
+#endif
 #pragma unroll
     for (int i = 0; i < M; i++) {
       Gl[i] = g[i];
